@@ -11,7 +11,14 @@ random-init weights. N>1: one process per GPU, DDP over RCCL ("nccl"), B=8
 per rank (weak scaling); under torchrun the ranks come from its environment,
 otherwise ``--gpus N`` starts the N rank processes itself (launch_ranks).
 
-Output: ONE JSON line on rank 0 with the driver's contract fields plus
+A plain run sets up, runs the W warm-up steps, times the K steps, writes the
+last timed step's outputs when ``--dump-outputs DIR`` is given, and prints ONE
+JSON line on rank 0 with the driver's contract fields (``metric``, ``value``,
+``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step``, ...); every field
+below is ``null`` there. ``--full`` adds the measurements that take runs or
+events of their own:
+* ``phases`` -- fwd + loss + bwd and the optimizer step apart (HIP events on
+  the step stream inside the timed region);
 * ``roofline`` — the dominant hot-path call site (largest summed time per
   step): algorithmic bytes per launch / its mean launch
   duration, measured with HIP events on the launch stream around every
@@ -32,8 +39,16 @@ Output: ONE JSON line on rank 0 with the driver's contract fields plus
   kernel from the committed rocprofv3 PMC passes (profiles/*_pmc_traffic.json,
   tools/pmc_traffic.py) when they cover that kernel and shape.
 
+``--dump-outputs DIR`` (rank 0): what a caller of the timed step holds after
+its last timed step, as float32 ``DIR/<name>.npy``: ``loss`` (the step's
+return value), ``params`` and ``grads`` (every parameter / its gradient,
+flattened and concatenated in ``named_parameters()`` order). Frames and initial
+weights are seeded, so two builds run with the same arguments see the same
+inputs. Above 64 MB in all, each array is a fixed seeded sample of its elements.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
-                       [--config kitti|sintel_mf] [--no-cpu-baseline]
+                       [--config kitti|sintel_mf] [--dump-outputs DIR]
+                       [--full [--no-cpu-baseline] [--no-replay]]
        python bench.py --device cpu --gpus 2 ...   (launcher test on gloo, tests/)
 """
 from __future__ import annotations
@@ -54,6 +69,19 @@ import re  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
+# Set-up time. MIOpen ships no tuned gfx950 database, so the first time it meets each of the
+# step's 272 (convolution configuration, direction) pairs it runs and times every applicable
+# solver and keeps the fastest in the user's find database. Its naive direct solvers
+# (ConvDirectNaiveConv{Fwd,Bwd,Wrw}: the reference implementation, one thread per output
+# element, up to seconds per launch on the weight gradients of the full-size levels) are
+# candidates too, never the fastest, and took 37 s of the 67 s a run spent before its first
+# timed step on empty user directories. Leaving them out of the search leaves 30 s; the
+# winners are Winograd / assembly implicit GEMM / 1x1 GEMM, and ms_per_step and the outputs
+# are unchanged. With the user directories filled nothing is searched either way (5-7 s).
+# setdefault: an explicit setting of the caller's still holds. Rank processes inherit it.
+for _naive in ("FWD", "BWD", "WRW"):
+    os.environ.setdefault(f"MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_{_naive}", "0")
+
 HBM_PEAK_GBPS = 8000.0  # MI355X spec (MI355X_MICROARCH.md); ~6300 measured copy
 CONFIGS = {
     "kitti": dict(H=256, W=832, workload="PWCLite fwd(with_bk)+unFlowLoss+bwd+Adam, KITTI 832x256, d=4"),
@@ -68,13 +96,18 @@ def parse():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=8, help="pairs per GPU (kitti_base.json train.batch_size)")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="kitti")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure phases, per call site times, the roofline, the SURVEY configs and the "
+                         "CPU baseline (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, parameters and gradients as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-steps", type=int, default=10,
                     help="timed CPU steps (each timed on its own: the spread is reported)")
     ap.add_argument("--cpu-batch", type=int, default=8,
                     help="CPU baseline batch: the GPU's per-rank B=8 (BASELINE.md 3)")
     ap.add_argument("--no-replay", action="store_true",
-                    help="skip the graph-replay device times (keeps a rocprofv3 run to real steps only)")
+                    help="--full: skip the graph-replay device times (keeps a rocprofv3 run to real steps only)")
     ap.add_argument("--cudnn-benchmark", action="store_true",
                     help="MIOpen find-mode tuning of the convolutions (slow first steps)")
     ap.add_argument("--per-direction", action="store_true",
@@ -377,6 +410,33 @@ def cpu_baseline(args, cfg_name):
     }
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, loss, module):
+    """--dump-outputs: the timed step's return value and the state it leaves with
+    its caller (parameters after the update, the gradients it applied), float32
+    .npy. Over the budget, every array keeps the same seeded sample of positions
+    from run to run."""
+    import numpy as np
+
+    named = [(n, p) for n, p in module.named_parameters() if p.requires_grad]
+    arrays = {
+        "loss": loss.detach().float().reshape(1).cpu().numpy(),
+        "params": torch.cat([p.detach().float().reshape(-1) for _, p in named]).cpu().numpy(),
+        "grads": torch.cat([(torch.zeros_like(p) if p.grad is None else p.grad).detach().float().reshape(-1)
+                            for _, p in named]).cpu().numpy(),
+    }
+    budget = DUMP_BUDGET_BYTES // len(arrays)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > budget:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, budget // 4, replace=False))
+            a = a[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def _free_port():
     import socket
 
@@ -502,7 +562,8 @@ def main():
     # so their per-site times come from the eager pass after the timed region.
     site_pass = None
     roof_site = None
-    if on_gpu and not use_graph:
+    full = args.full
+    if full and on_gpu and not use_graph:
         with KernelTimer() as site_pass:
             for _ in range(max(3, min(args.steps, 10))):
                 run()
@@ -514,9 +575,9 @@ def main():
     if distributed:
         dist.barrier()
     sync()
-    if on_gpu and not use_graph:
+    if full and on_gpu and not use_graph:
         step.phase_events = []  # (start, after backward, end) device events per timed step
-    with KernelTimer(enabled=on_gpu and not use_graph and roof_site is not None,
+    with KernelTimer(enabled=full and on_gpu and not use_graph and roof_site is not None,
                      only={roof_site}) as kt:
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -525,7 +586,9 @@ def main():
     if distributed:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    if use_graph:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, step.module)
+    if full and use_graph:
         # per-site kernel times: the same step run eagerly for K steps with HIP
         # events around every library launch (kernel durations do not depend on
         # how the launch was issued; rocprofv3 of the replays cross-checks them)
@@ -552,7 +615,7 @@ def main():
     loss_val = float(loss.item())
 
     rows = roof = per_op_us = gpu_configs = None
-    if on_gpu:
+    if full and on_gpu:
         if site_pass is not None:
             # per-site rows from the untimed pass; the roofline site's mean from
             # the timed region itself (its launches only were bracketed there)
@@ -577,7 +640,7 @@ def main():
         gpu_configs = None if args.no_replay else survey_configs_gpu(device)
 
     cpu = None
-    if on_gpu and rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and on_gpu and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, args.config)
 
     if rank == 0:
@@ -598,6 +661,7 @@ def main():
             "dtype": "f32",
             "data": "synthetic U[0,1) frame pairs, random-init PWCLite weights",
             "execution": "hip-graph replay of the captured step" if use_graph else "eager",
+            "full": full,
             "config": {
                 "workload": c["workload"],
                 "global_batch": args.batch * world,

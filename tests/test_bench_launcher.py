@@ -41,6 +41,42 @@ def test_bench_spawns_two_ranks_on_gloo(config):
     assert out["final_loss"] == out["final_loss"]  # finite (not NaN)
 
 
+@pytest.mark.timeout(600)
+def test_bench_dump_outputs_is_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's loss / params / grads as
+    float32 .npy; two runs with the same arguments start from the same frames
+    and weights, so they write the same arrays. --steps sets the timed steps,
+    and a plain run reports none of the --full measurements."""
+    import numpy as np
+
+    outs = []
+    for d in ("a", "b"):
+        p = _run(["--device", "cpu", "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "1",
+                  "--hw", "64", "128", "--dump-outputs", str(tmp_path / d)])
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        outs.append(json.loads(lines[0]))
+    out = outs[0]
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["full"] is False
+    assert out["ms_per_step"] > 0
+    assert abs(out["value"] * out["ms_per_step"] / 1e3 - 1.0) < 1e-2  # batch 1: pairs/s x s/step == 1
+    for k in ("phases", "levels", "roofline", "cpu_baseline", "survey_configs", "hot_path_us_per_step"):
+        assert out[k] is None, k
+    assert sorted(f.name for f in (tmp_path / "a").iterdir()) == ["grads.npy", "loss.npy", "params.npy"]
+    total = 0
+    for name in ("loss", "params", "grads"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == b.shape and np.isfinite(a).all(), name
+        assert np.abs(a).max() > 0, name
+        # same inputs, same host code: equal up to the thread-order rounding of fp32 sums
+        np.testing.assert_allclose(a, b, rtol=1e-4, atol=1e-6, err_msg=name)
+        total += a.nbytes
+    assert total <= 64 * 1000 * 1000
+    assert np.load(tmp_path / "a" / "params.npy").shape == np.load(tmp_path / "a" / "grads.npy").shape
+    assert abs(float(np.load(tmp_path / "a" / "loss.npy")[0]) - out["final_loss"]) <= 1e-5
+
+
 @pytest.mark.timeout(300)
 def test_bench_rejects_mismatched_world():
     """Under an external launcher, --gpus must equal WORLD_SIZE (no silent one-rank run)."""

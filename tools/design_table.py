@@ -1,4 +1,4 @@
-"""Markdown per-site table for DESIGN.md §5 from a bench.py line and its PMC
+"""Markdown per-site table for DESIGN.md §5 from a bench.py --full line and its PMC
 traffic summary: python tools/design_table.py profiles/<tag>_bench.json [profiles/<tag>_pmc_traffic.json]"""
 import json
 import sys

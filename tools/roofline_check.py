@@ -1,6 +1,6 @@
 """Cross-check bench.py's roofline timing against rocprofv3.
 
-Reads the JSON line of a bench.py run made under
+Reads the JSON line of a ``bench.py --full`` run made under
 ``USF_ROCTX=1 rocprofv3 --kernel-trace --stats --kernel-rename --marker-trace``
 and that run's kernel_stats.csv, where every hot-path launch is listed under
 its call-site name (unsamflow_amd.kernel_timer.site_name). Prints, for the
@@ -12,7 +12,7 @@ final reduction -- is the sum of both).
 
 The profiler inflates the in-step time of two-kernel sites (the gap between
 their kernels), so the profiled run's own largest site can differ from the
-unprofiled bench's. With a third argument (the unprofiled bench.py line) the
+unprofiled bench's. With a third argument (the unprofiled bench.py --full line) the
 check is made for THAT run's roofline site and also reports its unprofiled
 in-step mean.
 
