@@ -152,6 +152,37 @@ _SIGNATURES = {
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
+# the census entries (include/unsamflow_hip_census.h): the same library, their
+# own header and version, so USF_ABI_VERSION and the table above stay as they are
+CENSUS_API_VERSION = 1
+CENSUS_SYMBOLS = {
+    "usf_census_api_version": ([], ctypes.c_int),
+    "usf_census_loss_partials": ([ctypes.c_int] * 3, ctypes.c_int),
+    "usf_census_loss_fwd_f32": (
+        [_c_float_p] * 4 + [ctypes.c_longlong, _c_float_p, _c_float_p, _c_float_p] + [ctypes.c_int] * 5
+        + [ctypes.c_float, ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+    "usf_census_loss_pair_fwd_f32": (
+        [_c_float_p] * 5 + [ctypes.c_longlong, _c_float_p, _c_float_p, _c_float_p] + [ctypes.c_int] * 5
+        + [ctypes.c_float, ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+    "usf_census_loss_bwd_f32": ([_c_float_p] * 4 + [ctypes.c_int] * 4 + [ctypes.c_void_p], ctypes.c_int),
+    "usf_census_loss_pyramid_partials": ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int],
+                                         ctypes.c_longlong),
+    "usf_census_loss_pyramid_fwd_f32": (
+        [ctypes.c_int] + [ctypes.c_void_p] * 8 + [_c_float_p, ctypes.c_longlong, _c_float_p, ctypes.c_void_p]
+        + [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+    "usf_census_loss_pyramid_bwd_f32": (
+        [ctypes.c_int, ctypes.c_void_p, _c_float_p, _c_float_p] + [ctypes.c_void_p] * 3 + [ctypes.c_int,
+                                                                                            ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+}
+
 _lock = threading.Lock()
 _lib = None
 _load_error: str | None = None
@@ -176,13 +207,16 @@ def load() -> ctypes.CDLL:
             )
             raise RuntimeError(_load_error)
         lib = ctypes.CDLL(str(_LIB_PATH), mode=ctypes.RTLD_LOCAL)
-        for name, (argtypes, restype) in _SIGNATURES.items():
+        for name, (argtypes, restype) in {**_SIGNATURES, **CENSUS_SYMBOLS}.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = restype
         v = lib.usf_abi_version()
         if v != ABI_VERSION:
             raise RuntimeError(f"libunsamflow_hip.so ABI version {v} != expected {ABI_VERSION}")
+        v = lib.usf_census_api_version()
+        if v != CENSUS_API_VERSION:
+            raise RuntimeError(f"libunsamflow_hip.so census API version {v} != expected {CENSUS_API_VERSION}")
         _lib = lib
         return lib
 

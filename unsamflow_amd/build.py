@@ -24,8 +24,9 @@ INCLUDE_DIR = PKG_DIR.parent / "include"
 ARCH = os.environ.get("USF_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-SOURCES = ["corr.hip", "warp.hip", "photo.hip", "upsample.hip", "convex.hip", "stream.hip", "capi.cpp"]
+SOURCES = ["corr.hip", "warp.hip", "photo.hip", "census.hip", "upsample.hip", "convex.hip", "stream.hip", "capi.cpp"]
 HEADERS = ["usf_common.h", "warp_tap.h", "interp_tap.h"]
+PUBLIC_HEADERS = ["unsamflow_hip.h", "unsamflow_hip_census.h"]  # the C ABI (include/)
 
 # -fno-slp-vectorize: the SLP vectorizer packs the kernels' independent FMAs into
 # v_pk_fma_f32 / v_pk_add_f32, whose operands must sit in aligned register pairs:
@@ -55,7 +56,7 @@ def build_id() -> str:
     summaries (tools/pmc_traffic.py), so bench.py never reports a traffic
     figure measured on another build."""
     h = hashlib.sha256()
-    for f in [CSRC / s for s in SOURCES] + [CSRC / s for s in HEADERS] + [INCLUDE_DIR / "unsamflow_hip.h"]:
+    for f in [CSRC / s for s in SOURCES] + [CSRC / s for s in HEADERS] + [INCLUDE_DIR / s for s in PUBLIC_HEADERS]:
         h.update(f.name.encode())
         h.update(f.read_bytes())
     h.update(" ".join(COMMON_FLAGS).encode())
@@ -78,7 +79,7 @@ def build_library(force: bool = False, verbose: bool = False) -> Path:
     LIB_DIR.mkdir(exist_ok=True)
     obj_dir = LIB_DIR / "obj"
     obj_dir.mkdir(exist_ok=True)
-    headers = [CSRC / h for h in HEADERS] + [INCLUDE_DIR / "unsamflow_hip.h"]
+    headers = [CSRC / h for h in HEADERS] + [INCLUDE_DIR / h for h in PUBLIC_HEADERS]
     bid = build_id()
     stamp = obj_dir / "build_id.txt"
     id_changed = not stamp.exists() or stamp.read_text().strip() != bid

@@ -8,6 +8,9 @@ reference's JSON configs:
 * ``sintel_base()`` — configs/sintel_base.json (same loss/model/train keys)
 * ``sintel_mf()``   — configs/sintel_aug+hg+mf.json:3-6 on top of sintel_base
   (mask-feature correlation branch, ``aggregation_type="concat"``)
+* ``kitti_stage1()`` / ``sintel_stage1()`` — the base config with its
+  ``train.stage1.loss`` overrides applied (from epoch 50 of 200: the census
+  term alone, bidirectional occlusion check)
 
 ``load_json`` reads a reference-format JSON file with the one-level
 ``base_configs`` inheritance + recursive merge of utils/config_parser.py:11-33.
@@ -116,4 +119,20 @@ def sintel_mf() -> AttrDict:
     cfg = sintel_base()
     cfg.model.add_mask_corr = True
     cfg.model.aggregation_type = "concat"
+    return cfg
+
+
+# train.stage1.loss of configs/kitti_base.json and configs/sintel_base.json
+_STAGE1_LOSS = {"occ_from_back": False, "w_l1": 0.0, "w_ssim": 0.0, "w_ternary": 1.0}
+
+
+def kitti_stage1() -> AttrDict:
+    cfg = kitti_base()
+    cfg.loss.update(_STAGE1_LOSS)
+    return cfg
+
+
+def sintel_stage1() -> AttrDict:
+    cfg = sintel_base()
+    cfg.loss.update(_STAGE1_LOSS)
     return cfg

@@ -9,6 +9,7 @@
 #include <cstdlib>
 
 #include "../../include/unsamflow_hip.h"
+#include "../../include/unsamflow_hip_census.h"
 #include "usf_common.h"
 
 namespace usf {
@@ -614,6 +615,166 @@ int usf_photo_loss_bwd_f32(const float* grad_basis, const float* coef, const flo
   if (const int pe = pre_check("usf_photo_loss_bwd_f32", (hipStream_t)stream)) return pe;
   return finish("usf_photo_loss_bwd_f32",
                 photo_bwd_launch(grad_basis, coef, grad_loss, grad_flow, B, H, W, ndir, (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+// ------------------------------------------------- unsamflow_hip_census.h --
+int usf_census_api_version(void) { return USF_CENSUS_API_VERSION; }
+
+int usf_census_loss_partials(int B, int H, int W) {
+  return (B > 0 && H > 0 && W > 0) ? census_partials(B, H, W) : 0;
+}
+
+// one direction's inputs; min_fbs = 2*H*W (one direction) or 4*H*W (a pair)
+static bool check_census(const char* fn, const float* src, const float* tgt, const float* mask, const float* flow,
+                         long long fbs, int planes, int B, int C, int H, int W, int pad_mode) {
+  if (!check_dims(fn, B, C, H, W)) return false;
+  if (C != 3) {
+    set_error("%s: C=%d image channels (the census transform needs 3)", fn, C);
+    return false;
+  }
+  if (H < 3 || W < 3) {
+    set_error("%s: H=%d W=%d has no interior pixel (H, W >= 3)", fn, H, W);
+    return false;
+  }
+  if (pad_mode != USF_PAD_ZEROS && pad_mode != USF_PAD_BORDER) {
+    set_error("%s: unknown pad_mode %d", fn, pad_mode);
+    return false;
+  }
+  if (!src || !tgt || !mask || !flow) {
+    set_error("%s: null input pointer", fn);
+    return false;
+  }
+  if (fbs < (long long)planes * H * W && B > 1) {
+    set_error("%s: flow batch stride %lld < %d*H*W", fn, fbs, planes);
+    return false;
+  }
+  return true;
+}
+
+int usf_census_loss_fwd_f32(const float* src, const float* tgt, const float* mask, const float* flow,
+                            long long flow_bstride, float* partials, float* out, float* grad_basis, int B, int C,
+                            int H, int W, int pad_mode, float w_ternary, void* stream) {
+  clear_error();
+  const char* fn = "usf_census_loss_fwd_f32";
+  if (!check_census(fn, src, tgt, mask, flow, flow_bstride, 2, B, C, H, W, pad_mode)) return USF_EINVAL;
+  if (!partials || !out) {
+    set_error("%s: null output pointer", fn);
+    return USF_EINVAL;
+  }
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn,
+                census_fwd_launch(src, tgt, mask, flow, flow_bstride, partials, out, grad_basis, B, H, W, pad_mode,
+                                  w_ternary, (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+int usf_census_loss_pair_fwd_f32(const float* im1, const float* im2, const float* mask1, const float* mask2,
+                                 const float* flow, long long flow_bstride, float* partials, float* out,
+                                 float* grad_basis, int B, int C, int H, int W, int pad_mode, float w_ternary,
+                                 void* stream) {
+  clear_error();
+  const char* fn = "usf_census_loss_pair_fwd_f32";
+  if (!check_census(fn, im1, im2, mask1, flow, flow_bstride, 4, B, C, H, W, pad_mode)) return USF_EINVAL;
+  if (!mask2) {
+    set_error("%s: null input pointer", fn);
+    return USF_EINVAL;
+  }
+  if (!partials || !out) {
+    set_error("%s: null output pointer", fn);
+    return USF_EINVAL;
+  }
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn,
+                census_pair_fwd_launch(im1, im2, mask1, mask2, flow, flow_bstride, partials, out, grad_basis, B, H, W,
+                                       pad_mode, w_ternary, (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+long long usf_census_loss_pyramid_partials(int nscale, const int* H, const int* W, int B) {
+  if (nscale < 1 || nscale > 4 || !H || !W || B <= 0) return 0;
+  long long n = 0;
+  for (int k = 0; k < nscale; ++k) {
+    if (H[k] <= 0 || W[k] <= 0) return 0;
+    n += 2LL * census_partials(B, H[k], W[k]);
+  }
+  return n;
+}
+
+int usf_census_loss_pyramid_fwd_f32(int nscale, const float* const* im1, const float* const* im2,
+                                    const float* const* mask1, const float* const* mask2, const float* const* flow,
+                                    const long long* flow_bstride, const int* H, const int* W, float* partials,
+                                    long long partials_floats, float* out, float* const* grad_basis, int B, int C,
+                                    int pad_mode, float w_ternary, void* stream) {
+  clear_error();
+  const char* fn = "usf_census_loss_pyramid_fwd_f32";
+  if (nscale < 1 || nscale > 4 || !im1 || !im2 || !mask1 || !mask2 || !flow || !flow_bstride || !H || !W) {
+    set_error("%s: nscale %d not in [1,4] or a null array", fn, nscale);
+    return USF_EINVAL;
+  }
+  for (int k = 0; k < nscale; ++k) {
+    if (!check_census(fn, im1[k], im2[k], mask1[k], flow[k], flow_bstride[k], 4, B, C, H[k], W[k], pad_mode))
+      return USF_EINVAL;
+    if (!mask2[k]) {
+      set_error("%s: scale %d: null input pointer", fn, k);
+      return USF_EINVAL;
+    }
+    if (grad_basis && !grad_basis[k]) {
+      set_error("%s: scale %d: grad_basis given for some scales only", fn, k);
+      return USF_EINVAL;
+    }
+  }
+  if (!partials || !out || partials_floats < usf_census_loss_pyramid_partials(nscale, H, W, B)) {
+    set_error("%s: partials of %lld floats < usf_census_loss_pyramid_partials = %lld, or null out", fn,
+              partials_floats, usf_census_loss_pyramid_partials(nscale, H, W, B));
+    return USF_EINVAL;
+  }
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn,
+                census_pyr_fwd_launch(nscale, im1, im2, mask1, mask2, flow, flow_bstride, H, W, partials, out,
+                                      grad_basis, B, pad_mode, w_ternary, (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+int usf_census_loss_pyramid_bwd_f32(int nscale, const float* const* grad_basis, const float* coef,
+                                    const float* grad_loss, float* const* grad_flow, const int* H, const int* W,
+                                    int B, void* stream) {
+  clear_error();
+  const char* fn = "usf_census_loss_pyramid_bwd_f32";
+  if (nscale < 1 || nscale > 4 || !grad_basis || !grad_flow || !H || !W || !coef || !grad_loss || B <= 0) {
+    set_error("%s: nscale %d not in [1,4], B=%d, or a null pointer", fn, nscale, B);
+    return USF_EINVAL;
+  }
+  for (int k = 0; k < nscale; ++k) {
+    if (!check_dims(fn, B, 4, H[k], W[k])) return USF_EINVAL;
+    if (!grad_basis[k] || !grad_flow[k]) {
+      set_error("%s: scale %d: null pointer", fn, k);
+      return USF_EINVAL;
+    }
+  }
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn,
+                census_pyr_bwd_launch(nscale, grad_basis, coef, grad_loss, grad_flow, H, W, B, 2, (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+int usf_census_loss_bwd_f32(const float* grad_basis, const float* coef, const float* grad_loss, float* grad_flow,
+                            int B, int H, int W, int ndir, void* stream) {
+  clear_error();
+  const char* fn = "usf_census_loss_bwd_f32";
+  if (!check_dims(fn, B, 4, H, W)) return USF_EINVAL;
+  if (ndir != 1 && ndir != 2) {
+    set_error("%s: ndir=%d (1 or 2)", fn, ndir);
+    return USF_EINVAL;
+  }
+  if (!grad_basis || !coef || !grad_loss || !grad_flow) {
+    set_error("%s: null pointer", fn);
+    return USF_EINVAL;
+  }
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn,
+                census_pyr_bwd_launch(1, &grad_basis, coef, grad_loss, &grad_flow, &H, &W, B, ndir,
+                                      (hipStream_t)stream),
                 (hipStream_t)stream);
 }
 

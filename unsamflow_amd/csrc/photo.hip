@@ -166,7 +166,6 @@ __global__ __launch_bounds__(256) void photo_bwd_kernel(const float* __restrict_
 // strip (R chosen per shape, strip_plan) and 2 columns either side.
 constexpr int kSL = 64;        // lanes of a strip = staged columns
 constexpr int kSO = kSL - 4;   // own columns per strip (lanes 2 .. 61)
-constexpr int kOffNone = 0x7FFFFFF0;  // buffer offset past num_records: reads 0
 constexpr int kRsrcWord3 = 0x00020000;
 
 struct StripArgs {
@@ -217,50 +216,6 @@ __device__ __forceinline__ float ssim_sums(const Sums& s, float& al, float& be, 
   }
   return cl;
 }
-
-// The warp tap of warp_tap.h (same rounding, same results) with the border
-// clip as selects instead of branches, and the four corner byte offsets for
-// buffer loads: a masked corner gets an offset past num_records, which the
-// hardware reads as 0 (no value selects after the loads).
-struct TapB {
-  int onw, one, osw, ose;
-  float n, s, w, e, mx, my;
-};
-template <bool BORDER>
-__device__ __forceinline__ TapB make_tap_b(float u, float v, int x, int y, int H, int W) {
-#pragma clang fp contract(off)
-  TapB t;
-  const float wm1 = (float)(W - 1), hm1 = (float)(H - 1);
-  const float gx = 2.0f * ((float)x + u) / wm1 - 1.0f;
-  const float gy = 2.0f * ((float)y + v) / hm1 - 1.0f;
-  const float sx = wm1 / 2.0f, sy = hm1 / 2.0f;
-  float ix = (gx + 1.0f) * sx;
-  float iy = (gy + 1.0f) * sy;
-  t.mx = sx;
-  t.my = sy;
-  if (BORDER) {
-    const bool xlo = !(ix > 0.f), xhi = ix >= wm1, ylo = !(iy > 0.f), yhi = iy >= hm1;
-    ix = xlo ? 0.f : (xhi ? wm1 : ix);
-    iy = ylo ? 0.f : (yhi ? hm1 : iy);
-    t.mx = (xlo || xhi) ? 0.f : sx;
-    t.my = (ylo || yhi) ? 0.f : sy;
-  }
-  const float fx = floorf(ix), fy = floorf(iy);
-  t.w = ix - fx;
-  t.e = 1.0f - t.w;
-  t.n = iy - fy;
-  t.s = 1.0f - t.n;
-  const int xw = (int)fx, yn = (int)fy;
-  const bool vxw = (unsigned)xw < (unsigned)W, vxe = (unsigned)(xw + 1) < (unsigned)W;
-  const bool vyn = (unsigned)yn < (unsigned)H, vys = (unsigned)(yn + 1) < (unsigned)H;
-  const int o = 4 * (yn * W + xw);
-  t.onw = vxw && vyn ? o : kOffNone;
-  t.one = vxe && vyn ? o + 4 : kOffNone;
-  t.osw = vxw && vys ? o + 4 * W : kOffNone;
-  t.ose = vxe && vys ? o + 4 * W + 4 : kOffNone;
-  return t;
-}
-
 
 // ------------------------------------------------ producer / consumer pair --
 // photo_pc_kernel: the strip stream above split over a PAIR of

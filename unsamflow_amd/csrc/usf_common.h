@@ -149,6 +149,22 @@ hipError_t photo_pyr_bwd_launch(int nscale, const float* const* basis, const flo
 hipError_t photo_bwd_launch(const float* basis, const float* coef, const float* gloss, float* gflow,
                             int B, int H, int W, int ndir, hipStream_t s);
 
+// census.hip: the ternary (census) photometric term; partials per direction
+int census_partials(int B, int H, int W);
+hipError_t census_fwd_launch(const float* src, const float* tgt, const float* mask, const float* flow,
+                             long long flow_bstride, float* partials, float* out, float* basis, int B, int H,
+                             int W, int pad_mode, float w_ternary, hipStream_t s);
+hipError_t census_pair_fwd_launch(const float* im1, const float* im2, const float* mask1, const float* mask2,
+                                  const float* flow, long long flow_bstride, float* partials, float* out,
+                                  float* basis, int B, int H, int W, int pad_mode, float w_ternary, hipStream_t s);
+hipError_t census_pyr_fwd_launch(int nscale, const float* const* im1, const float* const* im2,
+                                 const float* const* mask1, const float* const* mask2, const float* const* flow,
+                                 const long long* fbs, const int* H, const int* W, float* partials, float* out,
+                                 float* const* basis, int B, int pad_mode, float w_ternary, hipStream_t s);
+// every scale's [B, 2 ndir, H, W] basis -> gradient in one launch (ndir = 1 or 2)
+hipError_t census_pyr_bwd_launch(int nscale, const float* const* basis, const float* coef, const float* gloss,
+                                 float* const* gflow, const int* H, const int* W, int B, int ndir, hipStream_t s);
+
 hipError_t upsample_fwd_launch(const float* x, float* out, int B, int C, int H, int W, int k,
                                hipStream_t s);
 hipError_t upsample_bwd_launch(const float* gout, float* gx, int B, int C, int H, int W, int k,

@@ -63,4 +63,50 @@ __device__ __forceinline__ inline Tap make_tap(float u, float v, int x, int y, i
   return t;
 }
 
+constexpr int kOffNone = 0x7FFFFFF0;  // buffer offset past num_records: reads 0
+
+// The same tap (same rounding, same results) for the streaming loss kernels
+// (photo.hip, census.hip), with the border
+// clip as selects instead of branches, and the four corner byte offsets for
+// buffer loads: a masked corner gets an offset past num_records, which the
+// hardware reads as 0 (no value selects after the loads).
+struct TapB {
+  int onw, one, osw, ose;
+  float n, s, w, e, mx, my;
+};
+template <bool BORDER>
+__device__ __forceinline__ TapB make_tap_b(float u, float v, int x, int y, int H, int W) {
+#pragma clang fp contract(off)
+  TapB t;
+  const float wm1 = (float)(W - 1), hm1 = (float)(H - 1);
+  const float gx = 2.0f * ((float)x + u) / wm1 - 1.0f;
+  const float gy = 2.0f * ((float)y + v) / hm1 - 1.0f;
+  const float sx = wm1 / 2.0f, sy = hm1 / 2.0f;
+  float ix = (gx + 1.0f) * sx;
+  float iy = (gy + 1.0f) * sy;
+  t.mx = sx;
+  t.my = sy;
+  if (BORDER) {
+    const bool xlo = !(ix > 0.f), xhi = ix >= wm1, ylo = !(iy > 0.f), yhi = iy >= hm1;
+    ix = xlo ? 0.f : (xhi ? wm1 : ix);
+    iy = ylo ? 0.f : (yhi ? hm1 : iy);
+    t.mx = (xlo || xhi) ? 0.f : sx;
+    t.my = (ylo || yhi) ? 0.f : sy;
+  }
+  const float fx = floorf(ix), fy = floorf(iy);
+  t.w = ix - fx;
+  t.e = 1.0f - t.w;
+  t.n = iy - fy;
+  t.s = 1.0f - t.n;
+  const int xw = (int)fx, yn = (int)fy;
+  const bool vxw = (unsigned)xw < (unsigned)W, vxe = (unsigned)(xw + 1) < (unsigned)W;
+  const bool vyn = (unsigned)yn < (unsigned)H, vys = (unsigned)(yn + 1) < (unsigned)H;
+  const int o = 4 * (yn * W + xw);
+  t.onw = vxw && vyn ? o : kOffNone;
+  t.one = vxe && vyn ? o + 4 : kOffNone;
+  t.osw = vxw && vys ? o + 4 * W : kOffNone;
+  t.ose = vxe && vys ? o + 4 * W + 4 : kOffNone;
+  return t;
+}
+
 }  // namespace usf

@@ -9,10 +9,12 @@ the bidirectional check), nearest-resized per scale; per scale with
 two flow halves (``flow[:, :2]`` / ``flow[:, 2:]``, :130-131), occlusion-aware
 photometric loss (L1 + SSIM + ternary, :33-50) averaged over the two
 directions; edge-aware 1st/2nd-order smoothness at scale 0 when ``w_sm > 0``.
-On a ROCm device with the library's warp and ``w_ternary == 0`` the warp +
-L1 + SSIM of each scale and direction is one fused autograd op
-(unsamflow_amd.photometric); ``fused_photometric=False``
-or an injected ``warp_fn`` keeps the torch composition.
+On a ROCm device with the library's warp the warp + L1 + SSIM of each scale
+and direction is one fused autograd op (unsamflow_amd.photometric, SURVEY §8f
+row 2) and the warp + ternary (census) term another (unsamflow_amd.census, the
+stage-1 loss); with mixed weights the two are added, as loss_photomatric adds
+its terms under one normaliser. ``fused_photometric=False`` or an injected
+``warp_fn`` keeps the torch composition.
 Returns ``(loss[None], l_ph[None], l_sm[None], flow_mean[None], vis1, vis2)``.
 
 ``smooth_type == "homography"`` needs OpenCV RANSAC on the host
@@ -123,10 +125,33 @@ class unFlowLoss(nn.Module):  # noqa: N801 (reference name)
         self.occ_bidir = occ_bidir_fn or (lambda f12, f21: warp_utils.get_occu_mask_bidirection(f12, f21))
 
     def _fused_photometric(self, flow) -> bool:
-        """Fused HIP warp+L1+SSIM (unsamflow_amd.photometric) when this loss uses the
-        library's own warp on a ROCm device and the photometric terms are L1/SSIM."""
+        """Fused HIP warp + L1/SSIM (unsamflow_amd.photometric) and warp + census
+        (unsamflow_amd.census) when this loss uses the library's own warp on a ROCm device."""
         c = self.cfg
-        return (self.fused and flow.is_cuda and c.w_ternary == 0 and c.w_l1 >= 0 and c.w_ssim >= 0)
+        return (self.fused and flow.is_cuda and c.w_ternary >= 0 and c.w_l1 >= 0 and c.w_ssim >= 0)
+
+    def _fused_terms(self):
+        """(L1/SSIM op runs, census op runs): loss_photomatric's ``w > 0`` tests;
+        with w_ternary == 0 the L1/SSIM op always runs."""
+        c = self.cfg
+        return c.w_ternary == 0 or c.w_l1 > 0 or c.w_ssim > 0, c.w_ternary > 0
+
+    def _fused_losses(self, kind, *args):
+        """The fused ops' ``kind`` form ("single", "pair", "pyramid") on ``args``:
+        the L1/SSIM op, the census op, or their sum."""
+        from . import census, photometric
+
+        c = self.cfg
+        photo, tern = self._fused_terms()
+        fp = {"single": photometric.photometric_loss, "pair": photometric.photometric_loss_pair,
+              "pyramid": photometric.photometric_loss_pyramid}[kind]
+        ft = {"single": census.ternary_loss, "pair": census.ternary_loss_pair,
+              "pyramid": census.ternary_loss_pyramid}[kind]
+        out = fp(*args, c.warp_pad, c.w_l1, c.w_ssim) if photo else None
+        if tern:
+            lt = ft(*args, c.warp_pad, c.w_ternary)
+            out = lt if out is None else out + lt
+        return out
 
     def loss_photomatric(self, im1_scaled, im1_recons, vis_mask1):
         c = self.cfg
@@ -200,18 +225,16 @@ class unFlowLoss(nn.Module):  # noqa: N801 (reference name)
 
         zero = torch.zeros((), dtype=torch.float32, device=dev)  # a fill, not an H2D copy (graph-capturable)
         # with_bk on the library's kernels: every weighted scale's photometric
-        # pair in ONE launch (photometric_loss_pyramid; the per-scale results,
-        # the small scales filling the chip's tail)
+        # pair in ONE launch per fused op (photometric_loss_pyramid / ternary_loss_pyramid;
+        # the per-scale results, the small scales filling the chip's tail)
         pyr_losses = {}
         scales = [i for i, f in enumerate(pyramid_flows) if c.w_ph_scales[i] > 0]
         if (PHOTO_PYRAMID and c.with_bk and pyr1 is not None and 1 < len(scales) <= 4 and occ_aware
                 and all(self._fused_photometric(pyramid_flows[i]) for i in scales)):
-            from .photometric import photometric_loss_pyramid
-
             hws = [tuple(pyramid_flows[i].shape[-2:]) for i in scales]
-            lp = photometric_loss_pyramid([pyramid_flows[i] for i in scales], [pyr1[hw] for hw in hws],
-                                          [pyr2[hw] for hw in hws], [vis1_pyr[i] for i in scales],
-                                          [vis2_pyr[i] for i in scales], c.warp_pad, c.w_l1, c.w_ssim)
+            lp = self._fused_losses("pyramid", [pyramid_flows[i] for i in scales], [pyr1[hw] for hw in hws],
+                                    [pyr2[hw] for hw in hws], [vis1_pyr[i] for i in scales],
+                                    [vis2_pyr[i] for i in scales])
             pyr_losses = {i: (lp[k, 0] + lp[k, 1]) / 2.0 for k, i in enumerate(scales)}
         warp_losses, smooth_losses = [], []
         for i, flow in enumerate(pyramid_flows):
@@ -233,13 +256,11 @@ class unFlowLoss(nn.Module):  # noqa: N801 (reference name)
                     m1 = torch.ones((b, 1, h, w), dtype=torch.float32, device=dev)
                     m2 = torch.ones((b, 1, h, w), dtype=torch.float32, device=dev)
                 if self._fused_photometric(flow):
-                    from .photometric import photometric_loss, photometric_loss_pair
-
                     if c.with_bk:  # both directions in one launch
-                        lp = photometric_loss_pair(flow, im1_s, im2_s, m1, m2, c.warp_pad, c.w_l1, c.w_ssim)
+                        lp = self._fused_losses("pair", flow, im1_s, im2_s, m1, m2)
                         lw = (lp[0] + lp[1]) / 2.0
                     else:
-                        lw = photometric_loss(flow[:, :2], im2_s, im1_s, m1, c.warp_pad, c.w_l1, c.w_ssim)
+                        lw = self._fused_losses("single", flow[:, :2], im2_s, im1_s, m1)
                 else:
                     im1_rec = self.warp(im2_s, flow[:, :2], pad=c.warp_pad)
                     im2_rec = self.warp(im1_s, flow[:, 2:], pad=c.warp_pad)

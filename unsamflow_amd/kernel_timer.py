@@ -211,9 +211,21 @@ def site_launcher(op: str, key, device, seed: int = 0):
         coef = torch.rand(3 * ndir, device=device, generator=g)
         gl = torch.ones(ndir, device=device)
         return lambda: ops.photo_loss_backward(basis, coef, gl)
-    if op in ("photo_pyr", "photo_pyr_grad", "photo_pyr_bwd"):  # the loss scales in one launch
+    if op == "census_bwd":
+        B, ndir, H, W = key
+        basis = torch.randn(B, 2 * ndir, H, W, device=device, generator=g)
+        coef = torch.rand(2 * ndir, device=device, generator=g)
+        gl = torch.ones(ndir, device=device)
+        return lambda: ops.census_loss_backward(basis, coef, gl)
+    if op in ("photo_pyr", "photo_pyr_grad", "photo_pyr_bwd", "census_pyr", "census_pyr_grad", "census_pyr_bwd"):
+        # the loss scales in one launch
         B, C = key[:2]
-        hw = [(key[i], key[i + 1]) for i in range(2, len(key) - (op != "photo_pyr_bwd"), 2)]
+        hw = [(key[i], key[i + 1]) for i in range(2, len(key) - (not op.endswith("_bwd")), 2)]
+        if op == "census_pyr_bwd":
+            bases = [torch.randn(B, 4, h, w, device=device, generator=g) for h, w in hw]
+            coef = torch.rand(4 * len(hw), device=device, generator=g)
+            gl = torch.ones(2 * len(hw), device=device)
+            return lambda: ops.census_loss_pyramid_backward(bases, coef, gl)
         if op == "photo_pyr_bwd":
             bases = [torch.randn(B, 8, h, w, device=device, generator=g) for h, w in hw]
             coef = torch.rand(6 * len(hw), device=device, generator=g)
@@ -230,6 +242,9 @@ def site_launcher(op: str, key, device, seed: int = 0):
             i2.append(torch.rand(B, C, h, w, device=device, generator=g))
             m1.append((torch.rand(B, 1, h, w, device=device, generator=g) > 0.1).float())
             m2.append(m1[-1].flip(-1).contiguous())
+        if op.startswith("census"):
+            return lambda: ops.census_loss_pyramid_forward(flows, i1, i2, m1, m2, key[-1],
+                                                           need_grad=op == "census_pyr_grad")
         return lambda: ops.photo_loss_pyramid_forward(flows, i1, i2, m1, m2, key[-1], need_grad=op == "photo_pyr_grad")
     if op == "occ_vis_pair":  # both directions of the loss's masks from a [B,4,H,W] flow
         B, _, H, W = key[:4]
@@ -239,7 +254,8 @@ def site_launcher(op: str, key, device, seed: int = 0):
         f2 = torch.sin(2 * xx + ph) + torch.cos(3 * yy - ph)
         flow4 = torch.cat([f2, -f2], 1).contiguous()
         return lambda: ops.occ_vis_pair(flow4, 0.2)
-    if op in ("occ_bwd", "splat", "photo_fwd", "photo_fwd_grad", "photo_pair", "photo_pair_grad"):
+    if op in ("occ_bwd", "splat", "photo_fwd", "photo_fwd_grad", "photo_pair", "photo_pair_grad", "census_fwd",
+              "census_fwd_grad", "census_pair", "census_pair_grad"):
         B, C, H, W = key[:4]
         yy = torch.linspace(0, 6.2832, H, device=device).view(1, 1, H, 1)
         xx = torch.linspace(0, 6.2832, W, device=device).view(1, 1, 1, W)
@@ -253,11 +269,16 @@ def site_launcher(op: str, key, device, seed: int = 0):
         src = torch.rand(B, C, H, W, device=device, generator=g)
         tgt = torch.rand(B, C, H, W, device=device, generator=g)
         mask = (torch.rand(B, 1, H, W, device=device, generator=g) > 0.1).float()
-        if op.startswith("photo_pair"):
+        if op.endswith(("_pair", "_pair_grad")):
             flow4 = torch.cat([flow, -flow], 1)
             mask2 = mask.flip(-1).contiguous()
+            if op.startswith("census"):
+                return lambda: ops.census_loss_pair_forward(flow4, tgt, src, mask, mask2, pad,
+                                                            need_grad=op == "census_pair_grad")
             return lambda: ops.photo_loss_pair_forward(flow4, tgt, src, mask, mask2, pad,
                                                        need_grad=op == "photo_pair_grad")
+        if op.startswith("census"):
+            return lambda: ops.census_loss_forward(src, tgt, mask, flow, pad, need_grad=op == "census_fwd_grad")
         return lambda: ops.photo_loss_forward(src, tgt, mask, flow, pad, need_grad=op == "photo_fwd_grad")
     B, C, H, W, pad = key[:5]
     x = torch.rand(B, C, H, W, device=device, generator=g)

@@ -568,6 +568,177 @@ def photo_loss_backward(basis, coef, grad_loss):
     return gflow
 
 
+def _census_args(src, tgt, mask, flow):
+    out = _photo_args(src, tgt, mask, flow)
+    C, H, W = out[-3:]
+    if C != 3:
+        raise NotImplementedError(f"fused census loss needs C = 3 image channels, got {C}")
+    if H < 3 or W < 3:
+        raise ValueError(f"fused census loss needs H, W >= 3 (an interior pixel), got {(H, W)}")
+    return out
+
+
+def census_loss_forward(src, tgt, mask, flow, pad: str = "border", w_ternary: float = 1.0,
+                        need_grad: bool = False):
+    """Fused warp + occlusion-aware ternary (census) loss of one scale and
+    direction (flow_loss.py:127-148, loss_blocks.py:12-50) -> (out, basis):
+    ``out`` = tensor [2] on the device {loss, c_t}; with ``need_grad``
+    ``basis`` = [B,2,H,W], the per-pixel flow-gradient basis computed in the
+    same pass (dL/dflow = c_t * basis), else None."""
+    if pad not in PAD_MODES:
+        raise NotImplementedError(f"flow_warp padding mode {pad!r} (supported: border, zeros)")
+    s, t, m, fv, fbs, B, C, H, W = _census_args(src, tgt, mask, flow)
+    lib = _lib.load()
+    partials = torch.empty(lib.usf_census_loss_partials(B, H, W), device=src.device, dtype=torch.float32)
+    out = torch.empty(2, device=src.device, dtype=torch.float32)
+    basis = torch.empty((B, 2, H, W), device=src.device, dtype=torch.float32) if need_grad else None
+    # algorithmic bytes: src, tgt, mask, flow read once; the basis written once
+    nbytes = 4 * B * H * W * (2 * C + 3 + (2 if need_grad else 0))
+    op = "census_fwd_grad" if need_grad else "census_fwd"
+    _args = (s.data_ptr(), t.data_ptr(), m.data_ptr(), fv.data_ptr(), fbs, partials.data_ptr(), out.data_ptr(),
+             basis.data_ptr() if need_grad else None, B, C, H, W, PAD_MODES[pad], float(w_ternary),
+             _lib.stream_handle(src.device),)
+    with torch.cuda.device(src.device), _kt.timed(op, (B, C, H, W, pad), src.device, nbytes):
+        rc = lib.usf_census_loss_fwd_f32(*_args)
+    _lib.check(rc, "usf_census_loss_fwd_f32")
+    return out, basis
+
+
+def _census_pair_args(flow, im1, im2, mask1, mask2):
+    a, b_, m1, B, C, H, W = _census_args(im1, im2, mask1, None)
+    m2 = mask2.contiguous()
+    _require_device_f32("mask2", m2)
+    _require_device_f32("flow", flow)
+    if tuple(m2.shape) != (B, 1, H, W):
+        raise ValueError(f"mask2 {tuple(m2.shape)} does not match {(B, 1, H, W)}")
+    if tuple(flow.shape) != (B, 4, H, W):
+        raise ValueError(f"flow must be [B,4,H,W] = {(B, 4, H, W)}, got {tuple(flow.shape)}")
+    fv = flow if flow[0].is_contiguous() else flow.contiguous()
+    return fv, a, b_, m1, m2, B, C, H, W, fv.stride(0) if B > 1 else 4 * H * W
+
+
+def census_loss_pair_forward(flow, im1, im2, mask1, mask2, pad: str = "border", w_ternary: float = 1.0,
+                             need_grad: bool = False):
+    """Both directions of a with_bk scale in one launch (flow_loss.py:130-131):
+    direction 0 = loss(im1, warp(im2, flow[:, :2]), mask1), direction 1 =
+    loss(im2, warp(im1, flow[:, 2:]), mask2) -> (out [4] = {loss, c_t} per
+    direction, basis [B,4,H,W] (= [B,2,2,H,W]) or None)."""
+    if pad not in PAD_MODES:
+        raise NotImplementedError(f"flow_warp padding mode {pad!r} (supported: border, zeros)")
+    fv, a, b_, m1, m2, B, C, H, W, fbs = _census_pair_args(flow, im1, im2, mask1, mask2)
+    lib = _lib.load()
+    partials = torch.empty(2 * lib.usf_census_loss_partials(B, H, W), device=a.device, dtype=torch.float32)
+    out = torch.empty(4, device=a.device, dtype=torch.float32)
+    basis = torch.empty((B, 4, H, W), device=a.device, dtype=torch.float32) if need_grad else None
+    # algorithmic bytes (each input read once): im1 and im2 (2C), the 4-channel
+    # flow, both masks; with the gradient the 4 basis planes written once
+    nbytes = 4 * B * H * W * (2 * C + 4 + 2 + (4 if need_grad else 0))
+    op = "census_pair_grad" if need_grad else "census_pair"
+    _args = (a.data_ptr(), b_.data_ptr(), m1.data_ptr(), m2.data_ptr(), fv.data_ptr(), fbs, partials.data_ptr(),
+             out.data_ptr(), basis.data_ptr() if need_grad else None, B, C, H, W, PAD_MODES[pad], float(w_ternary),
+             _lib.stream_handle(a.device),)
+    with torch.cuda.device(a.device), _kt.timed(op, (B, C, H, W, pad), a.device, nbytes):
+        rc = lib.usf_census_loss_pair_fwd_f32(*_args)
+    _lib.check(rc, "usf_census_loss_pair_fwd_f32")
+    return out, basis
+
+
+def census_loss_pyramid_forward(flows, im1s, im2s, masks1, masks2, pad: str = "border", w_ternary: float = 1.0,
+                                need_grad: bool = False):
+    """:func:`census_loss_pair_forward` for up to 4 loss scales in one launch
+    (usf_census_loss_pyramid_fwd_f32; the largest scale first) -> (out
+    [nscale, 4] = {loss, c_t} per direction per scale, bases: a list of
+    [B,4,H_k,W_k] or None)."""
+    import ctypes
+
+    if pad not in PAD_MODES:
+        raise NotImplementedError(f"flow_warp padding mode {pad!r} (supported: border, zeros)")
+    n = len(flows)
+    if not 1 <= n <= 4 or not (len(im1s) == len(im2s) == len(masks1) == len(masks2) == n):
+        raise ValueError(f"1..4 scales with one flow, two images and two masks each (got {n})")
+    args = [_census_pair_args(*x) for x in zip(flows, im1s, im2s, masks1, masks2)]
+    B, C = args[0][5], args[0][6]
+    if any(x[5] != B for x in args):
+        raise ValueError("every scale needs the same batch size")
+    dev = args[0][1].device
+    Hs = _host_array(ctypes.c_int, [x[7] for x in args])
+    Ws = _host_array(ctypes.c_int, [x[8] for x in args])
+    lib = _lib.load()
+    npart = int(lib.usf_census_loss_pyramid_partials(n, Hs, Ws, B))
+    partials = torch.empty(npart, device=dev, dtype=torch.float32)
+    out = torch.empty((n, 4), device=dev, dtype=torch.float32)
+    bases = [torch.empty((B, 4, x[7], x[8]), device=dev, dtype=torch.float32) for x in args] if need_grad else None
+    ptrs = lambda i: _host_array(ctypes.c_void_p, [x[i].data_ptr() for x in args])  # noqa: E731
+    nbytes = sum(4 * B * x[7] * x[8] * (2 * C + 4 + 2 + (4 if need_grad else 0)) for x in args)
+    op = "census_pyr_grad" if need_grad else "census_pyr"
+    key = (B, C) + tuple(v for x in args for v in (x[7], x[8])) + (pad,)
+    _args = (n, ptrs(1), ptrs(2), ptrs(3), ptrs(4), ptrs(0), _host_array(ctypes.c_longlong, [x[9] for x in args]),
+             Hs, Ws, partials.data_ptr(), npart, out.data_ptr(),
+             _host_array(ctypes.c_void_p, [t.data_ptr() for t in bases]) if need_grad else None, B, C,
+             PAD_MODES[pad], float(w_ternary), _lib.stream_handle(dev),)
+    with torch.cuda.device(dev), _kt.timed(op, key, dev, nbytes):
+        rc = lib.usf_census_loss_pyramid_fwd_f32(*_args)
+    _lib.check(rc, "usf_census_loss_pyramid_fwd_f32")
+    return out, bases
+
+
+def census_loss_pyramid_backward(bases, coef, grad_losses):
+    """d(loss)/d(flow_k) * grad for every scale of :func:`census_loss_pyramid_forward`
+    in one launch: bases [B,4,H_k,W_k], coef = its out [nscale, 4], grad_losses
+    [nscale, 2] -> list of [B,4,H_k,W_k] (deterministic)."""
+    import ctypes
+
+    n = len(bases)
+    for t in bases:
+        _require_device_f32("basis", t)
+        if t.dim() != 4 or t.shape[1] != 4:
+            raise ValueError(f"gradient basis must be [B,4,H,W], got {tuple(t.shape)}")
+    B = bases[0].shape[0]
+    dev = bases[0].device
+    gl = grad_losses.reshape(-1).to(torch.float32).contiguous()
+    if gl.numel() != 2 * n or coef.numel() != 4 * n:
+        raise ValueError(f"grad_losses / coef sizes {gl.numel()} / {coef.numel()} for {n} scales")
+    bases = [t.contiguous() for t in bases]
+    coef = coef.contiguous()
+    gflows = [torch.empty_like(t) for t in bases]
+    Hs = _host_array(ctypes.c_int, [t.shape[2] for t in bases])
+    Ws = _host_array(ctypes.c_int, [t.shape[3] for t in bases])
+    lib = _lib.load()
+    key = (B, 2) + tuple(v for t in bases for v in t.shape[2:])
+    nbytes = sum(4 * B * t.shape[2] * t.shape[3] * 8 for t in bases)
+    _args = (n, _host_array(ctypes.c_void_p, [t.data_ptr() for t in bases]), coef.data_ptr(), gl.data_ptr(),
+             _host_array(ctypes.c_void_p, [t.data_ptr() for t in gflows]), Hs, Ws, B, _lib.stream_handle(dev),)
+    with torch.cuda.device(dev), _kt.timed("census_pyr_bwd", key, dev, nbytes):
+        rc = lib.usf_census_loss_pyramid_bwd_f32(*_args)
+    _lib.check(rc, "usf_census_loss_pyramid_bwd_f32")
+    return gflows
+
+
+def census_loss_backward(basis, coef, grad_loss):
+    """d(census loss)/d(flow) * grad_loss from the forward's gradient basis
+    ([B,2,H,W] one direction, [B,4,H,W] a pair) and coefficients -> the same
+    shape (deterministic)."""
+    _require_device_f32("basis", basis)
+    B, K, H, W = _nchw("basis", basis)
+    if K not in (2, 4):
+        raise ValueError(f"gradient basis must be [B,2,H,W] or [B,4,H,W], got {tuple(basis.shape)}")
+    ndir = K // 2
+    basis = basis.contiguous()
+    coef = coef.contiguous()
+    gl = grad_loss.reshape(-1).to(torch.float32).contiguous()
+    if gl.numel() != ndir or coef.numel() != 2 * ndir:
+        raise ValueError(f"grad_loss / coef have {gl.numel()} / {coef.numel()} elements for {ndir} direction(s)")
+    gflow = torch.empty_like(basis)
+    lib = _lib.load()
+    _args = (basis.data_ptr(), coef.data_ptr(), gl.data_ptr(), gflow.data_ptr(), B, H, W, ndir,
+             _lib.stream_handle(basis.device),)
+    with torch.cuda.device(basis.device), _kt.timed("census_bwd", (B, ndir, H, W), basis.device,
+                                                      4 * B * H * W * 4 * ndir):
+        rc = lib.usf_census_loss_bwd_f32(*_args)
+    _lib.check(rc, "usf_census_loss_bwd_f32")
+    return gflow
+
+
 def _plane_slice_stride(name: str, t: torch.Tensor, shape) -> int:
     """Batch stride of a [B,K,H,W] channel slice whose per-sample planes are dense."""
     B, K, H, W = shape
