@@ -183,6 +183,26 @@ CENSUS_SYMBOLS = {
     ),
 }
 
+# the stage-1 augmentation entries (include/unsamflow_hip_ar.h), versioned the same way
+AR_API_VERSION = 1
+_ar_strided = [_c_float_p] + [ctypes.c_longlong] * 3 + [_c_float_p] + [ctypes.c_longlong] * 2
+AR_SYMBOLS = {
+    "usf_ar_api_version": ([], ctypes.c_int),
+    "usf_ar_transform_f32": (
+        [_c_float_p] * 3 + [ctypes.c_longlong] + [_c_float_p] * 8 + [ctypes.c_int] * 3 + [ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+    "usf_ar_loss_partials": ([ctypes.c_int] * 3, ctypes.c_int),
+    "usf_ar_loss_fwd_f32": (
+        [_c_float_p] + _ar_strided + [_c_float_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+    "usf_ar_loss_bwd_f32": (
+        [_c_float_p] + _ar_strided + [_c_float_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+}
+
 _lock = threading.Lock()
 _lib = None
 _load_error: str | None = None
@@ -207,7 +227,7 @@ def load() -> ctypes.CDLL:
             )
             raise RuntimeError(_load_error)
         lib = ctypes.CDLL(str(_LIB_PATH), mode=ctypes.RTLD_LOCAL)
-        for name, (argtypes, restype) in {**_SIGNATURES, **CENSUS_SYMBOLS}.items():
+        for name, (argtypes, restype) in {**_SIGNATURES, **CENSUS_SYMBOLS, **AR_SYMBOLS}.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = restype
@@ -217,6 +237,9 @@ def load() -> ctypes.CDLL:
         v = lib.usf_census_api_version()
         if v != CENSUS_API_VERSION:
             raise RuntimeError(f"libunsamflow_hip.so census API version {v} != expected {CENSUS_API_VERSION}")
+        v = lib.usf_ar_api_version()
+        if v != AR_API_VERSION:
+            raise RuntimeError(f"libunsamflow_hip.so AR API version {v} != expected {AR_API_VERSION}")
         _lib = lib
         return lib
 

@@ -11,6 +11,11 @@ reference's JSON configs:
 * ``kitti_stage1()`` / ``sintel_stage1()`` — the base config with its
   ``train.stage1.loss`` overrides applied (from epoch 50 of 200: the census
   term alone, bidirectional occlusion check)
+* ``kitti_stage1_ar()`` / ``sintel_stage1_ar()`` — the stage-1 config with its
+  ``train.stage1.train`` overrides applied as well (``run_atst``, ``run_st``,
+  ``run_ot``, ``ot_size``) and the train keys the augmentation branch reads
+  (``w_ar``, ``ar_eps``, ``ar_q``, ``mask_st``, ``st_cfg``): the step of
+  epochs 50-200 (unsamflow_amd.ar, harness.TrainStep)
 
 ``load_json`` reads a reference-format JSON file with the one-level
 ``base_configs`` inheritance + recursive merge of utils/config_parser.py:11-33.
@@ -135,4 +140,30 @@ def kitti_stage1() -> AttrDict:
 def sintel_stage1() -> AttrDict:
     cfg = sintel_base()
     cfg.loss.update(_STAGE1_LOSS)
+    return cfg
+
+
+# the train keys the augmentation branch reads (configs/*_base.json "train") with
+# train.stage1.train applied; st_cfg and ot_size differ between the data sets
+_AR_TRAIN = {"ar_eps": 0.0, "ar_q": 1.0, "key_obj_aug": False, "mask_st": True, "run_atst": True, "run_ot": True,
+             "run_st": True, "w_ar": 0.02}
+_ST_CFG_KITTI = {"add_noise": True, "hflip": True, "rotate": [-0.01, 0.01, -0.01, 0.01],
+                 "squeeze": [1.0, 1.0, 1.0, 1.0], "trans": [0.04, 0.005], "vflip": False,
+                 "zoom": [1.0, 1.4, 0.99, 1.01]}
+_ST_CFG_SINTEL = {"add_noise": True, "hflip": True, "rotate": [-0.2, 0.2, -0.015, 0.015],
+                  "squeeze": [0.86, 1.16, 1.0, 1.0], "trans": [0.2, 0.015], "vflip": True,
+                  "zoom": [1.0, 1.5, 0.985, 1.015]}
+
+
+def kitti_stage1_ar() -> AttrDict:
+    cfg = kitti_stage1()
+    cfg.train.update(AttrDict.wrap(dict(copy.deepcopy(_AR_TRAIN), ot_size=[192, 640],
+                                        st_cfg=copy.deepcopy(_ST_CFG_KITTI))))
+    return cfg
+
+
+def sintel_stage1_ar() -> AttrDict:
+    cfg = sintel_stage1()
+    cfg.train.update(AttrDict.wrap(dict(copy.deepcopy(_AR_TRAIN), ot_size=[320, 704],
+                                        st_cfg=copy.deepcopy(_ST_CFG_SINTEL))))
     return cfg

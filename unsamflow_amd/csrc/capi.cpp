@@ -9,6 +9,7 @@
 #include <cstdlib>
 
 #include "../../include/unsamflow_hip.h"
+#include "../../include/unsamflow_hip_ar.h"
 #include "../../include/unsamflow_hip_census.h"
 #include "usf_common.h"
 
@@ -775,6 +776,118 @@ int usf_census_loss_bwd_f32(const float* grad_basis, const float* coef, const fl
   return finish(fn,
                 census_pyr_bwd_launch(1, &grad_basis, coef, grad_loss, &grad_flow, &H, &W, B, ndir,
                                       (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+// ----------------------------------------------------- unsamflow_hip_ar.h --
+int usf_ar_api_version(void) { return USF_AR_API_VERSION; }
+
+// shape of the AR entries: [B,C,H,W] within the 32-bit per-sample offsets, H, W >= 2
+static bool check_ar_dims(const char* fn, int B, int C, int H, int W) {
+  if (!check_dims(fn, B, C, H, W)) return false;
+  if (H < 2 || W < 2) {
+    set_error("%s: H=%d W=%d (the normalised coordinates need H, W >= 2)", fn, H, W);
+    return false;
+  }
+  return true;
+}
+
+int usf_ar_transform_f32(const float* img1, const float* img2, const float* flow, long long flow_bstride,
+                         const float* mask, const float* theta, const float* noise1, const float* noise2,
+                         float* img1_t, float* img2_t, float* flow_t, float* mask_t, int B, int H, int W,
+                         void* stream) {
+  clear_error();
+  const char* fn = "usf_ar_transform_f32";
+  if (!check_ar_dims(fn, B, 3, H, W)) return USF_EINVAL;
+  if (B > 65535) {
+    set_error("%s: B=%d > 65535", fn, B);
+    return USF_EINVAL;
+  }
+  if (!img1 || !img2 || !flow || !mask || !theta) {
+    set_error("%s: null input pointer", fn);
+    return USF_EINVAL;
+  }
+  if (!img1_t || !img2_t || !flow_t || !mask_t) {
+    set_error("%s: null output pointer", fn);
+    return USF_EINVAL;
+  }
+  if (flow_bstride < 2LL * H * W && B > 1) {
+    set_error("%s: flow batch stride %lld < 2*H*W", fn, flow_bstride);
+    return USF_EINVAL;
+  }
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn,
+                ar_transform_launch(img1, img2, flow, flow_bstride, mask, theta, noise1, noise2, img1_t, img2_t,
+                                    flow_t, mask_t, B, H, W, (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+int usf_ar_loss_partials(int B, int H, int W) { return (B > 0 && H > 0 && W > 0) ? ar_loss_partials(B, H, W) : 0; }
+
+static bool check_ar_loss(const char* fn, const float* pred, const float* target, long long tbs, long long tcs,
+                          long long trs, const float* noc, long long nbs, long long nrs, int B, int H, int W,
+                          float eps, float q) {
+  if (!check_ar_dims(fn, B, 2, H, W)) return false;
+  if (B > 65535) {
+    set_error("%s: B=%d > 65535", fn, B);
+    return false;
+  }
+  if (!pred || !target || !noc) {
+    set_error("%s: null input pointer", fn);
+    return false;
+  }
+  if (tbs < 0 || tcs < 0 || trs < 0 || nbs < 0 || nrs < 0) {
+    set_error("%s: negative stride (target %lld/%lld/%lld, noc %lld/%lld)", fn, tbs, tcs, trs, nbs, nrs);
+    return false;
+  }
+  if (!(q > 0.f) || !(eps >= 0.f)) {
+    set_error("%s: q=%g eps=%g (need q > 0, eps >= 0)", fn, (double)q, (double)eps);
+    return false;
+  }
+  return true;
+}
+
+int usf_ar_loss_fwd_f32(const float* pred, const float* target, long long target_bstride, long long target_cstride,
+                        long long target_rstride, const float* noc, long long noc_bstride, long long noc_rstride,
+                        const float* denom, float* partials, float* out, int B, int H, int W, float eps, float q,
+                        void* stream) {
+  clear_error();
+  const char* fn = "usf_ar_loss_fwd_f32";
+  if (!check_ar_loss(fn, pred, target, target_bstride, target_cstride, target_rstride, noc, noc_bstride, noc_rstride,
+                     B, H, W, eps, q))
+    return USF_EINVAL;
+  if (!partials || !out) {
+    set_error("%s: null output pointer", fn);
+    return USF_EINVAL;
+  }
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn,
+                ar_loss_fwd_launch(pred, target, target_bstride, target_cstride, target_rstride, noc, noc_bstride,
+                                   noc_rstride, denom, partials, out, B, H, W, eps, q, (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+int usf_ar_loss_bwd_f32(const float* pred, const float* target, long long target_bstride, long long target_cstride,
+                        long long target_rstride, const float* noc, long long noc_bstride, long long noc_rstride,
+                        const float* coef, const float* grad_loss, float* grad_pred, int B, int H, int W, float eps,
+                        float q, void* stream) {
+  clear_error();
+  const char* fn = "usf_ar_loss_bwd_f32";
+  if (!check_ar_loss(fn, pred, target, target_bstride, target_cstride, target_rstride, noc, noc_bstride, noc_rstride,
+                     B, H, W, eps, q))
+    return USF_EINVAL;
+  if (!coef || !grad_loss) {
+    set_error("%s: null input pointer", fn);
+    return USF_EINVAL;
+  }
+  if (!grad_pred) {
+    set_error("%s: null output pointer", fn);
+    return USF_EINVAL;
+  }
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn,
+                ar_loss_bwd_launch(pred, target, target_bstride, target_cstride, target_rstride, noc, noc_bstride,
+                                   noc_rstride, coef, grad_loss, grad_pred, B, H, W, eps, q, (hipStream_t)stream),
                 (hipStream_t)stream);
 }
 

@@ -165,6 +165,19 @@ hipError_t census_pyr_fwd_launch(int nscale, const float* const* im1, const floa
 hipError_t census_pyr_bwd_launch(int nscale, const float* const* basis, const float* coef, const float* gloss,
                                  float* const* gflow, const int* H, const int* W, int B, int ndir, hipStream_t s);
 
+// ar.hip: the stage-1 augmentation branch (spatial transform, AR loss)
+hipError_t ar_transform_launch(const float* img1, const float* img2, const float* flow, long long flow_bstride,
+                               const float* mask, const float* theta, const float* noise1, const float* noise2,
+                               float* img1_t, float* img2_t, float* flow_t, float* mask_t, int B, int H, int W,
+                               hipStream_t s);
+int ar_loss_partials(int B, int H, int W);
+hipError_t ar_loss_fwd_launch(const float* pred, const float* target, long long tbs, long long tcs, long long trs,
+                              const float* noc, long long nbs, long long nrs, const float* denom, float* partials,
+                              float* out, int B, int H, int W, float eps, float q, hipStream_t s);
+hipError_t ar_loss_bwd_launch(const float* pred, const float* target, long long tbs, long long tcs, long long trs,
+                              const float* noc, long long nbs, long long nrs, const float* coef, const float* gloss,
+                              float* gpred, int B, int H, int W, float eps, float q, hipStream_t s);
+
 hipError_t upsample_fwd_launch(const float* x, float* out, int B, int C, int H, int W, int k,
                                hipStream_t s);
 hipError_t upsample_bwd_launch(const float* gout, float* gx, int B, int C, int H, int W, int k,

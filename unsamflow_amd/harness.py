@@ -15,6 +15,13 @@ frames, as ``/255`` images of datasets/flow_datasets.py:59-63). With
 ``ddp=True`` the model is wrapped in DistributedDataParallel (train.py:116-120):
 one process per GPU, gradient all-reduce over RCCL ("nccl" backend) / gloo.
 
+With ``cfg.train.run_atst`` / ``run_ot`` (config.*_stage1_ar(), the reference's
+epochs 50-200) the step adds the ARFlow branch of kitti_trainer_ar.py:137-249:
+the detached first-pass flow and its visibility mask are transformed by random
+affine maps together with the frames (unsamflow_amd.ar), a second pass
+(with_bk=False) on the transformed frames is held to the transformed flow by
+the AR loss, and a third pass does the same on a random crop.
+
 The per-step host syncs of the reference's logging (``loss.item()``,
 kitti_trainer_ar.py:284-293) are not part of the step.
 """
@@ -61,7 +68,7 @@ class TrainStep:
     def __init__(self, cfg, device, ddp: bool = False, corr_module=None, warp_fn: Callable | None = None,
                  loss_kwargs: dict | None = None, fused_adam: bool | None = None, seed: int = 42,
                  channels_last: bool = False, occ_backward_fn: Callable | None = None,
-                 capturable: bool = False):
+                 capturable: bool = False, fused_ar: bool = True):
         torch.manual_seed(seed)
         self.cfg = cfg
         self.device = torch.device(device)
@@ -96,22 +103,70 @@ class TrainStep:
         # triple of device events to: the optimizer step (clip + Adam + scheduler)
         # timed apart from fwd + loss + bwd (bench.py)
         self.phase_events: list | None = None
+        # the stage-1 augmentation branch (kitti_trainer_ar.py:137-249): off for every config without the keys
+        self.run_atst = bool(t.get("run_atst", False))
+        self.run_ot = bool(t.get("run_ot", False))
+        self.has_ar = self.run_atst or self.run_ot
+        self.l_atst = self.l_ot = None  # the last step's terms (detached)
+        if self.has_ar:
+            from .ar import RandomAffineFlow
 
-    def forward_loss(self, img1, img2, full_seg1=None, full_seg2=None):
+            # fused_ar: the HIP transform and loss on a ROCm device (the torch composition elsewhere);
+            # False: the torch composition everywhere
+            self.fused_ar = None if fused_ar else False
+            # thetas, crop offsets and the noise's std: one seeded host generator owned by the step
+            self.ar_generator = torch.Generator(device="cpu").manual_seed(seed)
+            self.sp_transform = RandomAffineFlow(t.st_cfg, addnoise=t.st_cfg.add_noise,
+                                                 generator=self.ar_generator, fused=self.fused_ar)
+
+    def forward_loss(self, img1, img2, full_seg1=None, full_seg2=None, img1_ph=None, img2_ph=None):
         res = self.model(img1, img2, full_seg1, full_seg2, with_bk=True)
         flows = [torch.cat([a, b], 1) for a, b in zip(res["flows_12"], res["flows_21"])]
         kw = {}
         if full_seg1 is not None:
             kw = dict(full_seg1=full_seg1, full_seg2=full_seg2)
-        loss, l_ph, l_sm, fmean, _, _ = self.loss_fn(flows, img1, img2, **kw)
-        return loss.mean(), flows
+        loss, l_ph, l_sm, fmean, vis1, _ = self.loss_fn(flows, img1, img2, **kw)
+        loss = loss.mean()
+        if self.has_ar:
+            loss = loss + self._ar_branch(res["flows_12"][0].detach(), vis1.detach(),
+                                          img1 if img1_ph is None else img1_ph, img2 if img2_ph is None else img2_ph)
+        return loss, flows
 
-    def __call__(self, img1, img2, full_seg1=None, full_seg2=None):
+    def _ar_branch(self, flow_ori, noc_ori, img1, img2):
+        """w_ar * (l_atst + l_ot): the second pass on the spatially transformed
+        frames and the third on a random crop, each held to the first pass's
+        (transformed / cropped) flow where it was visible."""
+        from .ar import ar_loss, random_crop
+
+        t = self.cfg.train
+        total = 0.0
+        self.l_atst = self.l_ot = None
+        if self.run_atst:
+            s = {"imgs": [img1, img2], "flows_f": [flow_ori], "masks_f": [noc_ori]}
+            if t.run_st:
+                s = self.sp_transform(s)
+            flow_t, noc_t = s["flows_f"][0], s["masks_f"][0]
+            pred = self.model(s["imgs"][0], s["imgs"][1], with_bk=False)["flows_12"][0]
+            if not t.mask_st:
+                noc_t = torch.ones_like(noc_t)
+            l_atst = ar_loss(pred, flow_t, noc_t, t.ar_eps, t.ar_q, fused=self.fused_ar)
+            total = total + t.w_ar * l_atst
+            self.l_atst = l_atst.detach()
+        if self.run_ot:
+            imgs, flow_ot, noc_ot = random_crop(torch.cat([img1, img2], 1), flow_ori, noc_ori, t.ot_size,
+                                                self.ar_generator)
+            pred = self.model(imgs[:, :3], imgs[:, 3:6], with_bk=False)["flows_12"][0]
+            l_ot = ar_loss(pred, flow_ot, noc_ot, t.ar_eps, t.ar_q, fused=self.fused_ar)
+            total = total + t.w_ar * l_ot
+            self.l_ot = l_ot.detach()
+        return total
+
+    def __call__(self, img1, img2, full_seg1=None, full_seg2=None, img1_ph=None, img2_ph=None):
         ev = None
         if self.phase_events is not None:
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
             ev[0].record()
-        loss, _ = self.forward_loss(img1, img2, full_seg1, full_seg2)
+        loss, _ = self.forward_loss(img1, img2, full_seg1, full_seg2, img1_ph, img2_ph)
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         if ev is not None:
@@ -181,6 +236,9 @@ class GraphedTrainStep:
                  group=None):
         import torch.distributed as dist
 
+        if getattr(step, "has_ar", False):
+            raise NotImplementedError("GraphedTrainStep: the stage-1 augmentation branch (run_atst / run_ot) is not "
+                                      "capturable (the crop offsets move pointers, the thetas are sampled on the host)")
         self.step = step
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1

@@ -739,6 +739,122 @@ def census_loss_backward(basis, coef, grad_loss):
     return gflow
 
 
+def ar_transform(img1, img2, flow, mask, theta, noise1=None, noise2=None):
+    """The stage-1 spatial transform of two frames, one flow and one mask in one
+    launch (usf_ar_transform_f32; sp_transforms.py:260-290): img1, img2
+    [B,3,H,W], flow [B,2,H,W] (a channel slice is used in place), mask
+    [B,1,H,W], theta [2,B,6] on the device, noise1 / noise2 None or [B,3,H,W]
+    already scaled -> (img1_t, img2_t, flow_t, mask_t)."""
+    for n, t in (("img1", img1), ("img2", img2), ("flow", flow), ("mask", mask), ("theta", theta)):
+        _require_device_f32(n, t)
+    B, C, H, W = _nchw("img1", img1)
+    if C != 3 or tuple(img2.shape) != (B, 3, H, W):
+        raise ValueError(f"img1 / img2 must be [B,3,H,W], got {tuple(img1.shape)} / {tuple(img2.shape)}")
+    if H < 2 or W < 2:
+        raise ValueError(f"the spatial transform needs H, W >= 2, got {(H, W)}")
+    if tuple(mask.shape) != (B, 1, H, W):
+        raise ValueError(f"mask {tuple(mask.shape)} does not match {(B, 1, H, W)}")
+    if tuple(theta.shape) != (2, B, 6):
+        raise ValueError(f"theta must be [2,B,6] = {(2, B, 6)}, got {tuple(theta.shape)}")
+    dev = img1.device
+    noise = []
+    for n, t in (("noise1", noise1), ("noise2", noise2)):
+        if t is not None:
+            _require_device_f32(n, t)
+            if tuple(t.shape) != (B, 3, H, W):
+                raise ValueError(f"{n} {tuple(t.shape)} does not match {(B, 3, H, W)}")
+            t = t.contiguous()
+        noise.append(t)
+    if any(t.device != dev for t in (img2, flow, mask, theta) + tuple(t for t in noise if t is not None)):
+        raise ValueError("the spatial transform's tensors are on different devices")
+    a, b_, m, th = img1.contiguous(), img2.contiguous(), mask.contiguous(), theta.contiguous()
+    fv, fbs = _flow_view(flow, B, H, W)
+    outs = (torch.empty_like(a), torch.empty_like(b_), torch.empty((B, 2, H, W), device=dev, dtype=torch.float32),
+            torch.empty_like(m))
+    lib = _lib.load()
+    # algorithmic bytes: 9 planes in and out, plus the noise planes read
+    nbytes = 4 * B * H * W * (18 + 3 * sum(t is not None for t in noise))
+    _args = (a.data_ptr(), b_.data_ptr(), fv.data_ptr(), fbs, m.data_ptr(), th.data_ptr(), _ptr(noise[0]),
+             _ptr(noise[1]), *[t.data_ptr() for t in outs], B, H, W, _lib.stream_handle(dev),)
+    with torch.cuda.device(dev), _kt.timed("ar_transform", (B, H, W, noise[0] is not None), dev, nbytes):
+        rc = lib.usf_ar_transform_f32(*_args)
+    _lib.check(rc, "usf_ar_transform_f32")
+    return outs
+
+
+def _ar_strided(name: str, t: torch.Tensor, shape) -> tuple[torch.Tensor, tuple]:
+    """(batch, channel, row) strides of a [B,K,H,W] view with unit column stride
+    -- what usf_ar_loss_* can address in place (a crop or channel slice, an
+    expanded mask). Any other layout is refused, never copied silently."""
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be a tensor of shape {tuple(shape)}, got "
+                         f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    s = t.stride()
+    if s[3] != 1:
+        raise ValueError(f"{name} has column stride {s[3]}: the AR loss entries take batch, channel and row strides "
+                         "with unit column stride (make it contiguous first)")
+    return t, (s[0], s[1], s[2])
+
+
+def _ar_loss_args(pred, target, noc, eps, q):
+    B, K, H, W = _nchw("pred", pred)
+    if K != 2:
+        raise ValueError(f"pred must be [B,2,H,W], got {tuple(pred.shape)}")
+    if not q > 0 or not eps >= 0:
+        raise ValueError(f"the AR loss needs q > 0 and eps >= 0, got q={q} eps={eps}")
+    target, ts = _ar_strided("target", target, (B, 2, H, W))
+    noc, ns = _ar_strided("noc", noc, (B, 1, H, W))
+    for n, t in (("pred", pred), ("target", target), ("noc", noc)):
+        _require_device_f32(n, t)
+    if target.device != pred.device or noc.device != pred.device:
+        raise ValueError("pred, target and noc are on different devices")
+    return pred.contiguous(), target, ts, noc, (ns[0], ns[2]), B, H, W
+
+
+def ar_loss_forward(pred, target, noc, eps: float = 0.0, q: float = 1.0, denom=None):
+    """``(((pred - target).abs() + eps) ** q * noc).mean() / (D + 1e-7)`` with D =
+    ``noc.mean()`` or the device scalar ``denom`` (kitti_trainer_ar.py:169-172)
+    -> out [2] on the device = {loss, c} (c: what the backward needs). target
+    [B,2,H,W] and noc [B,1,H,W] may be strided views with unit column stride."""
+    p, t, ts, n, ns, B, H, W = _ar_loss_args(pred, target, noc, eps, q)
+    dev = p.device
+    if denom is not None:
+        _require_device_f32("denom", denom)
+        if denom.numel() != 1 or denom.device != dev:
+            raise ValueError("denom must be one float32 element on pred's device")
+        denom = denom.reshape(1)
+    lib = _lib.load()
+    partials = torch.empty(lib.usf_ar_loss_partials(B, H, W), device=dev, dtype=torch.float32)
+    out = torch.empty(2, device=dev, dtype=torch.float32)
+    _args = (p.data_ptr(), t.data_ptr(), *ts, n.data_ptr(), *ns, _ptr(denom), partials.data_ptr(), out.data_ptr(),
+             B, H, W, float(eps), float(q), _lib.stream_handle(dev),)
+    # algorithmic bytes: pred and target (2 planes each) and noc read once
+    with torch.cuda.device(dev), _kt.timed("ar_loss_fwd", (B, H, W, float(q)), dev, 4 * B * H * W * 5):
+        rc = lib.usf_ar_loss_fwd_f32(*_args)
+    _lib.check(rc, "usf_ar_loss_fwd_f32")
+    return out
+
+
+def ar_loss_backward(pred, target, noc, coef, grad_loss, eps: float = 0.0, q: float = 1.0):
+    """d(AR loss)/d(pred) * grad_loss, recomputed from the forward's inputs in one
+    dense pass (coef = :func:`ar_loss_forward`'s out) -> [B,2,H,W]; sign(0) = 0."""
+    p, t, ts, n, ns, B, H, W = _ar_loss_args(pred, target, noc, eps, q)
+    dev = p.device
+    _require_device_f32("coef", coef)
+    gl = grad_loss.reshape(-1).to(torch.float32).contiguous()
+    if gl.numel() != 1 or coef.numel() != 2:
+        raise ValueError(f"grad_loss / coef have {gl.numel()} / {coef.numel()} elements (1 / 2)")
+    coef = coef.contiguous()
+    gpred = torch.empty_like(p)
+    lib = _lib.load()
+    _args = (p.data_ptr(), t.data_ptr(), *ts, n.data_ptr(), *ns, coef.data_ptr(), gl.data_ptr(), gpred.data_ptr(),
+             B, H, W, float(eps), float(q), _lib.stream_handle(dev),)
+    with torch.cuda.device(dev), _kt.timed("ar_loss_bwd", (B, H, W, float(q)), dev, 4 * B * H * W * 7):
+        rc = lib.usf_ar_loss_bwd_f32(*_args)
+    _lib.check(rc, "usf_ar_loss_bwd_f32")
+    return gpred
+
+
 def _plane_slice_stride(name: str, t: torch.Tensor, shape) -> int:
     """Batch stride of a [B,K,H,W] channel slice whose per-sample planes are dense."""
     B, K, H, W = shape
