@@ -464,177 +464,35 @@ int usf_occ_bidirection_f32(const float* flow12, long long flow12_bstride, const
                 (hipStream_t)stream);
 }
 
-int usf_photo_loss_partials(int B, int H, int W) {
-  return (B > 0 && H > 0 && W > 0) ? photo_partials(B, H, W) : 0;
-}
+// ------------------- the photometric losses: usf_photo_loss_*, usf_census_loss_* --
+// The two families take the same arguments in the same order (the census one
+// has one weight and fixes C = 3) and differ here only in what LossKind holds.
+struct LossKind {
+  const char* name;                      // usf_<name>_loss_*
+  bool census;                           // C == 3 and an interior pixel; else C <= 3
+  int basis_planes;                      // of the gradient basis, per direction
+  int (*partials)(int B, int H, int W);  // floats per direction
+  hipError_t (*bwd_launch)(int, const float* const*, const float*, const float*, float* const*, const int*,
+                           const int*, int, int, hipStream_t);
+};
+static const LossKind kPhoto{"photo", false, 4, photo_partials, photo_pyr_bwd_launch};
+static const LossKind kCensus{"census", true, 2, census_partials, census_pyr_bwd_launch};
 
-static bool check_photo(const char* fn, const float* src, const float* tgt, const float* mask,
-                        const float* flow, long long fbs, int B, int C, int H, int W, int pad_mode) {
+// one scale's inputs; planes = flow planes per sample: 2 (one direction; pass
+// mask2 = mask) or 4 (a pair)
+static bool check_loss_inputs(const char* fn, const LossKind& kind, const float* src, const float* tgt,
+                              const float* mask, const float* mask2, const float* flow, long long fbs, int planes,
+                              int B, int C, int H, int W, int pad_mode) {
   if (!check_dims(fn, B, C, H, W)) return false;
+  if (kind.census && C != 3) {
+    set_error("%s: C=%d image channels (the census transform needs 3)", fn, C);
+    return false;
+  }
   if (C > 3) {
     set_error("%s: C=%d image channels > 3", fn, C);
     return false;
   }
-  if (pad_mode != USF_PAD_ZEROS && pad_mode != USF_PAD_BORDER) {
-    set_error("%s: unknown pad_mode %d", fn, pad_mode);
-    return false;
-  }
-  if (!src || !tgt || !mask || !flow) {
-    set_error("%s: null input pointer", fn);
-    return false;
-  }
-  if (fbs < 2LL * H * W && B > 1) {
-    set_error("%s: flow batch stride %lld < 2*H*W", fn, fbs);
-    return false;
-  }
-  return true;
-}
-
-int usf_photo_loss_fwd_f32(const float* src, const float* tgt, const float* mask, const float* flow,
-                           long long flow_bstride, float* partials, float* out, float* grad_basis,
-                           int B, int C, int H, int W, int pad_mode, float w_l1, float w_ssim,
-                           void* stream) {
-  clear_error();
-  if (!check_photo("usf_photo_loss_fwd_f32", src, tgt, mask, flow, flow_bstride, B, C, H, W, pad_mode))
-    return USF_EINVAL;
-  if (!partials || !out) {
-    set_error("usf_photo_loss_fwd_f32: null output pointer");
-    return USF_EINVAL;
-  }
-  if (const int pe = pre_check("usf_photo_loss_fwd_f32", (hipStream_t)stream)) return pe;
-  return finish("usf_photo_loss_fwd_f32",
-                photo_fwd_launch(src, tgt, mask, flow, flow_bstride, partials, out, grad_basis, B, C,
-                                 H, W, pad_mode, w_l1, w_ssim, (hipStream_t)stream),
-                (hipStream_t)stream);
-}
-
-int usf_photo_loss_pair_fwd_f32(const float* im1, const float* im2, const float* mask1,
-                                const float* mask2, const float* flow, long long flow_bstride,
-                                float* partials, float* out, float* grad_basis, int B, int C, int H,
-                                int W, int pad_mode, float w_l1, float w_ssim, void* stream) {
-  clear_error();
-  const char* fn = "usf_photo_loss_pair_fwd_f32";
-  if (!check_photo(fn, im1, im2, mask1, flow, flow_bstride, B, C, H, W, pad_mode)) return USF_EINVAL;
-  if (!mask2) {
-    set_error("%s: null input pointer", fn);
-    return USF_EINVAL;
-  }
-  if (flow_bstride < 4LL * H * W && B > 1) {
-    set_error("%s: flow batch stride %lld < 4*H*W", fn, flow_bstride);
-    return USF_EINVAL;
-  }
-  if (!partials || !out) {
-    set_error("%s: null output pointer", fn);
-    return USF_EINVAL;
-  }
-  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
-  return finish(fn,
-                photo_pair_fwd_launch(im1, im2, mask1, mask2, flow, flow_bstride, partials, out,
-                                      grad_basis, B, C, H, W, pad_mode, w_l1, w_ssim,
-                                      (hipStream_t)stream),
-                (hipStream_t)stream);
-}
-
-long long usf_photo_loss_pyramid_partials(int nscale, const int* H, const int* W, int B) {
-  if (nscale < 1 || nscale > 4 || !H || !W || B <= 0) return 0;
-  long long n = 0;
-  for (int k = 0; k < nscale; ++k) {
-    if (H[k] <= 0 || W[k] <= 0) return 0;
-    n += 2LL * photo_partials(B, H[k], W[k]);
-  }
-  return n;
-}
-
-int usf_photo_loss_pyramid_fwd_f32(int nscale, const float* const* im1, const float* const* im2,
-                                   const float* const* mask1, const float* const* mask2, const float* const* flow,
-                                   const long long* flow_bstride, const int* H, const int* W, float* partials,
-                                   long long partials_floats, float* out, float* const* grad_basis, int B, int C,
-                                   int pad_mode, float w_l1, float w_ssim, void* stream) {
-  clear_error();
-  const char* fn = "usf_photo_loss_pyramid_fwd_f32";
-  if (nscale < 1 || nscale > 4 || !im1 || !im2 || !mask1 || !mask2 || !flow || !flow_bstride || !H || !W) {
-    set_error("%s: nscale %d not in [1,4] or a null array", fn, nscale);
-    return USF_EINVAL;
-  }
-  for (int k = 0; k < nscale; ++k) {
-    if (!check_photo(fn, im1[k], im2[k], mask1[k], flow[k], flow_bstride[k], B, C, H[k], W[k], pad_mode))
-      return USF_EINVAL;
-    if (!mask2[k] || (B > 1 && flow_bstride[k] < 4LL * H[k] * W[k])) {
-      set_error("%s: scale %d: null mask2 or flow batch stride %lld < 4*H*W", fn, k, flow_bstride[k]);
-      return USF_EINVAL;
-    }
-    if (grad_basis && !grad_basis[k]) {
-      set_error("%s: scale %d: grad_basis given for some scales only", fn, k);
-      return USF_EINVAL;
-    }
-  }
-  if (!partials || !out || partials_floats < usf_photo_loss_pyramid_partials(nscale, H, W, B)) {
-    set_error("%s: partials of %lld floats < usf_photo_loss_pyramid_partials = %lld, or null out", fn,
-              partials_floats, usf_photo_loss_pyramid_partials(nscale, H, W, B));
-    return USF_EINVAL;
-  }
-  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
-  return finish(fn,
-                photo_pyr_fwd_launch(nscale, im1, im2, mask1, mask2, flow, flow_bstride, H, W, partials, out,
-                                     grad_basis, B, C, pad_mode, w_l1, w_ssim, (hipStream_t)stream),
-                (hipStream_t)stream);
-}
-
-int usf_photo_loss_pyramid_bwd_f32(int nscale, const float* const* grad_basis, const float* coef,
-                                   const float* grad_loss, float* const* grad_flow, const int* H, const int* W, int B,
-                                   void* stream) {
-  clear_error();
-  const char* fn = "usf_photo_loss_pyramid_bwd_f32";
-  if (nscale < 1 || nscale > 4 || !grad_basis || !grad_flow || !H || !W || !coef || !grad_loss || B <= 0) {
-    set_error("%s: nscale %d not in [1,4], B=%d, or a null pointer", fn, nscale, B);
-    return USF_EINVAL;
-  }
-  for (int k = 0; k < nscale; ++k) {
-    if (!check_dims(fn, B, 8, H[k], W[k])) return USF_EINVAL;
-    if (!grad_basis[k] || !grad_flow[k]) {
-      set_error("%s: scale %d: null pointer", fn, k);
-      return USF_EINVAL;
-    }
-  }
-  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
-  return finish(fn, photo_pyr_bwd_launch(nscale, grad_basis, coef, grad_loss, grad_flow, H, W, B, (hipStream_t)stream),
-                (hipStream_t)stream);
-}
-
-int usf_photo_loss_bwd_f32(const float* grad_basis, const float* coef, const float* grad_loss,
-                           float* grad_flow, int B, int H, int W, int ndir, void* stream) {
-  clear_error();
-  if (!check_dims("usf_photo_loss_bwd_f32", B, 8, H, W)) return USF_EINVAL;
-  if (ndir != 1 && ndir != 2) {
-    set_error("usf_photo_loss_bwd_f32: ndir=%d (1 or 2)", ndir);
-    return USF_EINVAL;
-  }
-  if (!grad_basis || !coef || !grad_loss || !grad_flow) {
-    set_error("usf_photo_loss_bwd_f32: null pointer");
-    return USF_EINVAL;
-  }
-  if (const int pe = pre_check("usf_photo_loss_bwd_f32", (hipStream_t)stream)) return pe;
-  return finish("usf_photo_loss_bwd_f32",
-                photo_bwd_launch(grad_basis, coef, grad_loss, grad_flow, B, H, W, ndir, (hipStream_t)stream),
-                (hipStream_t)stream);
-}
-
-// ------------------------------------------------- unsamflow_hip_census.h --
-int usf_census_api_version(void) { return USF_CENSUS_API_VERSION; }
-
-int usf_census_loss_partials(int B, int H, int W) {
-  return (B > 0 && H > 0 && W > 0) ? census_partials(B, H, W) : 0;
-}
-
-// one direction's inputs; min_fbs = 2*H*W (one direction) or 4*H*W (a pair)
-static bool check_census(const char* fn, const float* src, const float* tgt, const float* mask, const float* flow,
-                         long long fbs, int planes, int B, int C, int H, int W, int pad_mode) {
-  if (!check_dims(fn, B, C, H, W)) return false;
-  if (C != 3) {
-    set_error("%s: C=%d image channels (the census transform needs 3)", fn, C);
-    return false;
-  }
-  if (H < 3 || W < 3) {
+  if (kind.census && (H < 3 || W < 3)) {
     set_error("%s: H=%d W=%d has no interior pixel (H, W >= 3)", fn, H, W);
     return false;
   }
@@ -642,7 +500,7 @@ static bool check_census(const char* fn, const float* src, const float* tgt, con
     set_error("%s: unknown pad_mode %d", fn, pad_mode);
     return false;
   }
-  if (!src || !tgt || !mask || !flow) {
+  if (!src || !tgt || !mask || !mask2 || !flow) {
     set_error("%s: null input pointer", fn);
     return false;
   }
@@ -653,16 +511,162 @@ static bool check_census(const char* fn, const float* src, const float* tgt, con
   return true;
 }
 
+static bool check_loss_outputs(const char* fn, const float* partials, const float* out) {
+  if (!partials || !out) set_error("%s: null output pointer", fn);
+  return partials && out;
+}
+
+static long long loss_pyramid_partials(const LossKind& kind, int nscale, const int* H, const int* W, int B) {
+  if (nscale < 1 || nscale > 4 || !H || !W || B <= 0) return 0;
+  long long n = 0;
+  for (int k = 0; k < nscale; ++k) {
+    if (H[k] <= 0 || W[k] <= 0) return 0;
+    n += 2LL * kind.partials(B, H[k], W[k]);
+  }
+  return n;
+}
+
+static bool check_loss_pyramid(const char* fn, const LossKind& kind, int nscale, const float* const* im1,
+                               const float* const* im2, const float* const* mask1, const float* const* mask2,
+                               const float* const* flow, const long long* fbs, const int* H, const int* W,
+                               const float* partials, long long partials_floats, const float* out,
+                               float* const* grad_basis, int B, int C, int pad_mode) {
+  if (nscale < 1 || nscale > 4 || !im1 || !im2 || !mask1 || !mask2 || !flow || !fbs || !H || !W) {
+    set_error("%s: nscale %d not in [1,4] or a null array", fn, nscale);
+    return false;
+  }
+  for (int k = 0; k < nscale; ++k) {
+    if (!check_loss_inputs(fn, kind, im1[k], im2[k], mask1[k], mask2[k], flow[k], fbs[k], 4, B, C, H[k], W[k],
+                           pad_mode))
+      return false;
+    if (grad_basis && !grad_basis[k]) {
+      set_error("%s: scale %d: grad_basis given for some scales only", fn, k);
+      return false;
+    }
+  }
+  const long long need = loss_pyramid_partials(kind, nscale, H, W, B);
+  if (!partials || !out || partials_floats < need) {
+    set_error("%s: partials of %lld floats < usf_%s_loss_pyramid_partials = %lld, or null out", fn, partials_floats,
+              kind.name, need);
+    return false;
+  }
+  return true;
+}
+
+// the backward of nscale scales of ndir directions each: checks and launch
+static int loss_bwd(const char* fn, const LossKind& kind, int nscale, const float* const* grad_basis,
+                    const float* coef, const float* grad_loss, float* const* grad_flow, const int* H, const int* W,
+                    int B, int ndir, void* stream) {
+  clear_error();
+  if (nscale < 1 || nscale > 4) {
+    set_error("%s: nscale %d not in [1,4]", fn, nscale);
+    return USF_EINVAL;
+  }
+  if (!grad_basis || !grad_flow || !H || !W || !coef || !grad_loss) {
+    set_error("%s: null pointer", fn);
+    return USF_EINVAL;
+  }
+  for (int k = 0; k < nscale; ++k) {
+    if (!check_dims(fn, B, 2 * kind.basis_planes, H[k], W[k])) return USF_EINVAL;
+    if (!grad_basis[k] || !grad_flow[k]) {
+      set_error("%s: scale %d: null pointer", fn, k);
+      return USF_EINVAL;
+    }
+  }
+  if (ndir != 1 && ndir != 2) {
+    set_error("%s: ndir=%d (1 or 2)", fn, ndir);
+    return USF_EINVAL;
+  }
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn, kind.bwd_launch(nscale, grad_basis, coef, grad_loss, grad_flow, H, W, B, ndir, (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+int usf_photo_loss_partials(int B, int H, int W) {
+  return (B > 0 && H > 0 && W > 0) ? photo_partials(B, H, W) : 0;
+}
+
+int usf_photo_loss_fwd_f32(const float* src, const float* tgt, const float* mask, const float* flow,
+                           long long flow_bstride, float* partials, float* out, float* grad_basis,
+                           int B, int C, int H, int W, int pad_mode, float w_l1, float w_ssim,
+                           void* stream) {
+  clear_error();
+  const char* fn = "usf_photo_loss_fwd_f32";
+  if (!check_loss_inputs(fn, kPhoto, src, tgt, mask, mask, flow, flow_bstride, 2, B, C, H, W, pad_mode) ||
+      !check_loss_outputs(fn, partials, out))
+    return USF_EINVAL;
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn,
+                photo_fwd_launch(src, tgt, mask, flow, flow_bstride, partials, out, grad_basis, B, C, H, W, pad_mode,
+                                 w_l1, w_ssim, (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+int usf_photo_loss_pair_fwd_f32(const float* im1, const float* im2, const float* mask1,
+                                const float* mask2, const float* flow, long long flow_bstride,
+                                float* partials, float* out, float* grad_basis, int B, int C, int H,
+                                int W, int pad_mode, float w_l1, float w_ssim, void* stream) {
+  clear_error();
+  const char* fn = "usf_photo_loss_pair_fwd_f32";
+  if (!check_loss_inputs(fn, kPhoto, im1, im2, mask1, mask2, flow, flow_bstride, 4, B, C, H, W, pad_mode) ||
+      !check_loss_outputs(fn, partials, out))
+    return USF_EINVAL;
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn,
+                photo_pair_fwd_launch(im1, im2, mask1, mask2, flow, flow_bstride, partials, out, grad_basis, B, C, H,
+                                      W, pad_mode, w_l1, w_ssim, (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+long long usf_photo_loss_pyramid_partials(int nscale, const int* H, const int* W, int B) {
+  return loss_pyramid_partials(kPhoto, nscale, H, W, B);
+}
+
+int usf_photo_loss_pyramid_fwd_f32(int nscale, const float* const* im1, const float* const* im2,
+                                   const float* const* mask1, const float* const* mask2, const float* const* flow,
+                                   const long long* flow_bstride, const int* H, const int* W, float* partials,
+                                   long long partials_floats, float* out, float* const* grad_basis, int B, int C,
+                                   int pad_mode, float w_l1, float w_ssim, void* stream) {
+  clear_error();
+  const char* fn = "usf_photo_loss_pyramid_fwd_f32";
+  if (!check_loss_pyramid(fn, kPhoto, nscale, im1, im2, mask1, mask2, flow, flow_bstride, H, W, partials,
+                          partials_floats, out, grad_basis, B, C, pad_mode))
+    return USF_EINVAL;
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn,
+                photo_pyr_fwd_launch(nscale, im1, im2, mask1, mask2, flow, flow_bstride, H, W, partials, out,
+                                     grad_basis, B, C, pad_mode, w_l1, w_ssim, (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+int usf_photo_loss_pyramid_bwd_f32(int nscale, const float* const* grad_basis, const float* coef,
+                                   const float* grad_loss, float* const* grad_flow, const int* H, const int* W, int B,
+                                   void* stream) {
+  return loss_bwd("usf_photo_loss_pyramid_bwd_f32", kPhoto, nscale, grad_basis, coef, grad_loss, grad_flow, H, W, B, 2,
+                  stream);
+}
+
+int usf_photo_loss_bwd_f32(const float* grad_basis, const float* coef, const float* grad_loss,
+                           float* grad_flow, int B, int H, int W, int ndir, void* stream) {
+  return loss_bwd("usf_photo_loss_bwd_f32", kPhoto, 1, &grad_basis, coef, grad_loss, &grad_flow, &H, &W, B, ndir,
+                  stream);
+}
+
+// ------------------------------------------------- unsamflow_hip_census.h --
+int usf_census_api_version(void) { return USF_CENSUS_API_VERSION; }
+
+int usf_census_loss_partials(int B, int H, int W) {
+  return (B > 0 && H > 0 && W > 0) ? census_partials(B, H, W) : 0;
+}
+
 int usf_census_loss_fwd_f32(const float* src, const float* tgt, const float* mask, const float* flow,
                             long long flow_bstride, float* partials, float* out, float* grad_basis, int B, int C,
                             int H, int W, int pad_mode, float w_ternary, void* stream) {
   clear_error();
   const char* fn = "usf_census_loss_fwd_f32";
-  if (!check_census(fn, src, tgt, mask, flow, flow_bstride, 2, B, C, H, W, pad_mode)) return USF_EINVAL;
-  if (!partials || !out) {
-    set_error("%s: null output pointer", fn);
+  if (!check_loss_inputs(fn, kCensus, src, tgt, mask, mask, flow, flow_bstride, 2, B, C, H, W, pad_mode) ||
+      !check_loss_outputs(fn, partials, out))
     return USF_EINVAL;
-  }
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn,
                 census_fwd_launch(src, tgt, mask, flow, flow_bstride, partials, out, grad_basis, B, H, W, pad_mode,
@@ -676,15 +680,9 @@ int usf_census_loss_pair_fwd_f32(const float* im1, const float* im2, const float
                                  void* stream) {
   clear_error();
   const char* fn = "usf_census_loss_pair_fwd_f32";
-  if (!check_census(fn, im1, im2, mask1, flow, flow_bstride, 4, B, C, H, W, pad_mode)) return USF_EINVAL;
-  if (!mask2) {
-    set_error("%s: null input pointer", fn);
+  if (!check_loss_inputs(fn, kCensus, im1, im2, mask1, mask2, flow, flow_bstride, 4, B, C, H, W, pad_mode) ||
+      !check_loss_outputs(fn, partials, out))
     return USF_EINVAL;
-  }
-  if (!partials || !out) {
-    set_error("%s: null output pointer", fn);
-    return USF_EINVAL;
-  }
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn,
                 census_pair_fwd_launch(im1, im2, mask1, mask2, flow, flow_bstride, partials, out, grad_basis, B, H, W,
@@ -693,13 +691,7 @@ int usf_census_loss_pair_fwd_f32(const float* im1, const float* im2, const float
 }
 
 long long usf_census_loss_pyramid_partials(int nscale, const int* H, const int* W, int B) {
-  if (nscale < 1 || nscale > 4 || !H || !W || B <= 0) return 0;
-  long long n = 0;
-  for (int k = 0; k < nscale; ++k) {
-    if (H[k] <= 0 || W[k] <= 0) return 0;
-    n += 2LL * census_partials(B, H[k], W[k]);
-  }
-  return n;
+  return loss_pyramid_partials(kCensus, nscale, H, W, B);
 }
 
 int usf_census_loss_pyramid_fwd_f32(int nscale, const float* const* im1, const float* const* im2,
@@ -709,27 +701,9 @@ int usf_census_loss_pyramid_fwd_f32(int nscale, const float* const* im1, const f
                                     int pad_mode, float w_ternary, void* stream) {
   clear_error();
   const char* fn = "usf_census_loss_pyramid_fwd_f32";
-  if (nscale < 1 || nscale > 4 || !im1 || !im2 || !mask1 || !mask2 || !flow || !flow_bstride || !H || !W) {
-    set_error("%s: nscale %d not in [1,4] or a null array", fn, nscale);
+  if (!check_loss_pyramid(fn, kCensus, nscale, im1, im2, mask1, mask2, flow, flow_bstride, H, W, partials,
+                          partials_floats, out, grad_basis, B, C, pad_mode))
     return USF_EINVAL;
-  }
-  for (int k = 0; k < nscale; ++k) {
-    if (!check_census(fn, im1[k], im2[k], mask1[k], flow[k], flow_bstride[k], 4, B, C, H[k], W[k], pad_mode))
-      return USF_EINVAL;
-    if (!mask2[k]) {
-      set_error("%s: scale %d: null input pointer", fn, k);
-      return USF_EINVAL;
-    }
-    if (grad_basis && !grad_basis[k]) {
-      set_error("%s: scale %d: grad_basis given for some scales only", fn, k);
-      return USF_EINVAL;
-    }
-  }
-  if (!partials || !out || partials_floats < usf_census_loss_pyramid_partials(nscale, H, W, B)) {
-    set_error("%s: partials of %lld floats < usf_census_loss_pyramid_partials = %lld, or null out", fn,
-              partials_floats, usf_census_loss_pyramid_partials(nscale, H, W, B));
-    return USF_EINVAL;
-  }
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn,
                 census_pyr_fwd_launch(nscale, im1, im2, mask1, mask2, flow, flow_bstride, H, W, partials, out,
@@ -740,43 +714,14 @@ int usf_census_loss_pyramid_fwd_f32(int nscale, const float* const* im1, const f
 int usf_census_loss_pyramid_bwd_f32(int nscale, const float* const* grad_basis, const float* coef,
                                     const float* grad_loss, float* const* grad_flow, const int* H, const int* W,
                                     int B, void* stream) {
-  clear_error();
-  const char* fn = "usf_census_loss_pyramid_bwd_f32";
-  if (nscale < 1 || nscale > 4 || !grad_basis || !grad_flow || !H || !W || !coef || !grad_loss || B <= 0) {
-    set_error("%s: nscale %d not in [1,4], B=%d, or a null pointer", fn, nscale, B);
-    return USF_EINVAL;
-  }
-  for (int k = 0; k < nscale; ++k) {
-    if (!check_dims(fn, B, 4, H[k], W[k])) return USF_EINVAL;
-    if (!grad_basis[k] || !grad_flow[k]) {
-      set_error("%s: scale %d: null pointer", fn, k);
-      return USF_EINVAL;
-    }
-  }
-  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
-  return finish(fn,
-                census_pyr_bwd_launch(nscale, grad_basis, coef, grad_loss, grad_flow, H, W, B, 2, (hipStream_t)stream),
-                (hipStream_t)stream);
+  return loss_bwd("usf_census_loss_pyramid_bwd_f32", kCensus, nscale, grad_basis, coef, grad_loss, grad_flow, H, W, B,
+                  2, stream);
 }
 
 int usf_census_loss_bwd_f32(const float* grad_basis, const float* coef, const float* grad_loss, float* grad_flow,
                             int B, int H, int W, int ndir, void* stream) {
-  clear_error();
-  const char* fn = "usf_census_loss_bwd_f32";
-  if (!check_dims(fn, B, 4, H, W)) return USF_EINVAL;
-  if (ndir != 1 && ndir != 2) {
-    set_error("%s: ndir=%d (1 or 2)", fn, ndir);
-    return USF_EINVAL;
-  }
-  if (!grad_basis || !coef || !grad_loss || !grad_flow) {
-    set_error("%s: null pointer", fn);
-    return USF_EINVAL;
-  }
-  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
-  return finish(fn,
-                census_pyr_bwd_launch(1, &grad_basis, coef, grad_loss, &grad_flow, &H, &W, B, ndir,
-                                      (hipStream_t)stream),
-                (hipStream_t)stream);
+  return loss_bwd("usf_census_loss_bwd_f32", kCensus, 1, &grad_basis, coef, grad_loss, &grad_flow, &H, &W, B, ndir,
+                  stream);
 }
 
 // ----------------------------------------------------- unsamflow_hip_ar.h --

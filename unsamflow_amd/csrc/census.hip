@@ -25,7 +25,7 @@
 // dI/dflow is the bilinear tap's coordinate derivative incl. norm_grid and the
 // border clip (warp_tap.h), the warp's own sample point.
 //
-// The forward streams photo.hip's column strips: 64 lanes = 64 staged columns
+// The forward streams photo.hip's column strips (strip.h): 64 lanes = 64 staged columns
 // (the 60 middle ones are the strip's own pixels), one staged row per step.
 // Here one wave runs a whole strip: the previous gray row, the pending G row
 // and the rows' flow derivatives live in registers, horizontal neighbours come
@@ -37,16 +37,13 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "strip.h"
 #include "usf_common.h"
 #include "warp_tap.h"
 
 namespace usf {
 namespace {
 
-constexpr int kSL = 64;       // lanes of a strip = staged columns
-constexpr int kSO = kSL - 4;  // own columns per strip (lanes 2 .. 61)
-constexpr int kRsrcWord3 = 0x00020000;
-constexpr int kMaxScales = 4;
 constexpr float kGrayR = 0.2989f, kGrayG = 0.5870f, kGrayB = 0.1140f;
 
 // one flow direction: rec = warp(src, flow), compared with tgt under mask
@@ -69,19 +66,6 @@ struct CensusPyr {
   int start[kMaxScales + 1];
 };
 
-// lane l reads lane l+1 / l-1 of the wave (DPP wave_shl:1 / wave_shr:1; the
-// missing neighbour of lane 63 / 0 reads 0). Every lane must be active.
-__device__ __forceinline__ float from_next(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float from_prev(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x138, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
-  return v;
-}
 __device__ __forceinline__ float ld(__amdgpu_buffer_rsrc_t r, int off, int soff) {
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, soff, 0));
 }
@@ -285,7 +269,7 @@ __device__ __forceinline__ void census_body(const CensusArgs& a, float* __restri
 template <bool BORDER, bool GRAD>
 __global__ __launch_bounds__(kSL) void census_fwd_kernel(CensusPyr m) {
   const int blk = blockIdx.x;
-  const int s = (blk >= m.start[1]) + (blk >= m.start[2]) + (blk >= m.start[3]);
+  const int s = strip_scale(m.start, blk);
   census_body<BORDER, GRAD>(m.sc[s], m.part[s], blk - m.start[s], m.start[s + 1] - m.start[s]);
 }
 
@@ -362,9 +346,7 @@ __global__ __launch_bounds__(256) void census_bwd_kernel(CensusBwd m, const floa
 // cheapest count wins, ties to fewer strips. The plan never depends on the
 // number of directions in the launch (it is made for two), so a pair and its
 // two single-direction calls sum the same partials.
-constexpr int kSimds = 1024;      // 256 CUs x 4 SIMDs
-constexpr int kMinStripRows = 4;  // the partials buffer holds ceil(H / 4) strips per column
-constexpr int kWaves = 4;         // resident strips per SIMD the plan assumes
+constexpr int kWaves = 4;  // resident strips per SIMD the plan assumes
 
 int strip_count(int B, int H, int W) {
   const long long cols = 2LL * B * ((W + kSO - 1) / kSO);
@@ -419,8 +401,7 @@ hipError_t census_launch(int nscale, const Scale* sc, int ndir, int B, int pad_m
     f.n[k] = (double)B * a.H * a.W;
     poff += (long long)ndir * census_partials(B, a.H, a.W);
   }
-  for (int k = nscale; k <= kMaxScales; ++k) m.start[k] = (int)total;
-  for (int k = nscale; k < kMaxScales; ++k) m.sc[k] = m.sc[0];  // never selected (start[k] = total)
+  strip_pad_scales(m, nscale, total);
   const dim3 grid(total), block(kSL);
   if (pad_mode == 1) {
     if (grad)

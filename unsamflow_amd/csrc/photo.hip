@@ -1,7 +1,7 @@
 // Fused occlusion-aware photometric loss of unFlowLoss for gfx950 (CDNA4):
 // the per-scale term of losses/flow_loss.py:127-148 with loss_photomatric
-// (:33-50) and SSIM (losses/loss_blocks.py:53-72), for one flow direction or
-// for both directions of a with_bk scale in one launch:
+// (:33-50) and SSIM (losses/loss_blocks.py:53-72), for one flow direction, for
+// both directions of a with_bk scale, or for up to 4 scales, in one launch:
 //
 //   rec  = flow_warp(src, flow, pad)                      (warp_utils.py:97-106)
 //   x    = rec * m,  y = tgt * m                          (SSIM arguments, :40)
@@ -31,14 +31,17 @@
 // backward and no warped image, SSIM map or dL/drec reaches HBM.
 // Deterministic: fixed-order sums, no atomics.
 //
-// The forward (photo_pc_kernel, below) streams column strips down the image,
+// The forward (photo_fwd_kernel, below) streams column strips down the image,
 // one staged row per step, split over a producer / consumer pair of waves.
 // Two earlier forms -- a 32x16 workgroup tile with a 2-pixel halo ring, and
 // one wave per strip -- were measured slower and removed.
+// There is one forward, one final and one backward kernel: the one-direction
+// and pair entries are one-scale launches of the pyramid's (photo_launch).
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 
+#include "strip.h"
 #include "usf_common.h"
 #include "warp_tap.h"
 
@@ -62,94 +65,6 @@ struct PhotoArgs {
   int B, C, H, W;
 };
 
-
-// One block per direction: fixed-order fp64 sum of its partials ->
-// out[3 dir ..] = {loss, c_l1, c_ssim}, c_* = w_* / (N_* * (mean(m) + 1e-6)).
-constexpr int kFinNT = 512;
-__global__ __launch_bounds__(kFinNT) void photo_final_kernel(const float* __restrict__ partials,
-                                                             int nblk, float* __restrict__ out,
-                                                             double n1, double n2, double n3,
-                                                             float w_l1, float w_ssim) {
-  __shared__ double red[3][kFinNT / 64];
-  const int t = threadIdx.x, dirn = blockIdx.x;
-  const float* p = partials + (size_t)3 * nblk * dirn;
-  double a = 0, b = 0, c = 0;
-  int i = t;
-  // 4 slots in flight per thread, summed in slot order (fixed)
-  for (; i + 3 * kFinNT < nblk; i += 4 * kFinNT) {
-    float v[4][3];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int q = 0; q < 3; ++q) v[j][q] = p[3 * (i + j * kFinNT) + q];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      a += v[j][0];
-      b += v[j][1];
-      c += v[j][2];
-    }
-  }
-  for (; i < nblk; i += kFinNT) {
-    a += p[3 * i];
-    b += p[3 * i + 1];
-    c += p[3 * i + 2];
-  }
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) {
-    a += __shfl_xor(a, s);
-    b += __shfl_xor(b, s);
-    c += __shfl_xor(c, s);
-  }
-  if ((t & 63) == 0) {
-    red[0][t >> 6] = a;
-    red[1][t >> 6] = b;
-    red[2][t >> 6] = c;
-  }
-  __syncthreads();
-  if (t == 0) {
-    double s0 = 0, s1 = 0, s2 = 0;
-    for (int w = 0; w < kFinNT / 64; ++w) {
-      s0 += red[0][w];
-      s1 += red[1][w];
-      s2 += red[2][w];
-    }
-    const double den = s2 / n3 + 1e-6;
-    const double l1 = n1 > 0 ? s0 / n1 : 0.0, ss = n2 > 0 ? s1 / n2 : 0.0;
-    float* o = out + 3 * dirn;
-    o[0] = (float)((w_l1 * l1 + w_ssim * ss) / den);
-    o[1] = n1 > 0 ? (float)(w_l1 / (n1 * den)) : 0.f;
-    o[2] = n2 > 0 ? (float)(w_ssim / (n2 * den)) : 0.f;
-  }
-}
-
-// --------------------------------------------------------------- backward --
-// gflow[b, 2 dir + j, p] = g_dir (c_l1 basis[b, 4 dir + j, p] + c_ssim basis[b, 4 dir + 2 + j, p])
-__global__ __launch_bounds__(256) void photo_bwd_kernel(const float* __restrict__ basis,
-                                                        const float* __restrict__ coef,
-                                                        const float* __restrict__ gloss,
-                                                        float* __restrict__ gflow, int HW, int ndir) {
-  const int dirn = blockIdx.z, b = blockIdx.y;
-  const float gl = gloss[dirn];
-  const float k1 = coef[3 * dirn + 1] * gl, k2 = coef[3 * dirn + 2] * gl;
-  const float* a = basis + ((size_t)b * ndir + dirn) * 4 * HW;
-  float* o = gflow + ((size_t)b * ndir + dirn) * 2 * HW;
-  const int i = (blockIdx.x * 256 + threadIdx.x) * 4;
-  if ((HW & 3) == 0) {
-    if (i >= HW) return;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const float4 u = *reinterpret_cast<const float4*>(a + j * HW + i);
-      const float4 v = *reinterpret_cast<const float4*>(a + (2 + j) * HW + i);
-      *reinterpret_cast<float4*>(o + j * HW + i) =
-          make_float4(k1 * u.x + k2 * v.x, k1 * u.y + k2 * v.y, k1 * u.z + k2 * v.z, k1 * u.w + k2 * v.w);
-    }
-  } else {
-    for (int e = i; e < i + 4 && e < HW; ++e)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) o[j * HW + e] = k1 * a[j * HW + e] + k2 * a[(2 + j) * HW + e];
-  }
-}
-
 // ------------------------------------------------------- strip (row-stream) --
 // A strip is 64 staged columns (lanes; the 60 middle ones are its own pixels)
 // by R own rows, streamed down one staged row per step:
@@ -164,26 +79,12 @@ __global__ __launch_bounds__(256) void photo_bwd_kernel(const float* __restrict_
 //                    complete its gradient basis.
 // Each staged pixel is warped once; the halo is 2 rows above and below each
 // strip (R chosen per shape, strip_plan) and 2 columns either side.
-constexpr int kSL = 64;        // lanes of a strip = staged columns
-constexpr int kSO = kSL - 4;   // own columns per strip (lanes 2 .. 61)
-constexpr int kRsrcWord3 = 0x00020000;
-
 struct StripArgs {
   PhotoDir dir[2];
   long long fbs, bbs;
   int B, H, W, R, nsx, nsy, ndir, nitems;
 };
 
-// lane l reads lane l+1 / l-1 of the wave (DPP wave_shl:1 / wave_shr:1;
-// the missing neighbour of lane 63 / 0 reads 0). Every lane must be active.
-// mov_dpp with bound_ctrl (no "old" operand to materialise), so the compiler
-// folds it into the add that consumes it (v_add_f32_dpp).
-__device__ __forceinline__ float from_next(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float from_prev(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x138, 0xf, 0xf, true));
-}
 __device__ __forceinline__ float hsum_next(float v) { return v + from_next(v + from_next(v)); }  // v[l]+v[l+1]+v[l+2]
 __device__ __forceinline__ float hsum_prev(float v) { return v + from_prev(v + from_prev(v)); }  // v[l]+v[l-1]+v[l-2]
 
@@ -218,7 +119,7 @@ __device__ __forceinline__ float ssim_sums(const Sums& s, float& al, float& be, 
 }
 
 // ------------------------------------------------ producer / consumer pair --
-// photo_pc_kernel: the strip stream above split over a PAIR of
+// photo_fwd_kernel: the strip stream above split over a PAIR of
 // waves, so each holds half the state and twice as many waves share a SIMD.
 // The producer stages rows (flow, tap, gathers, x = rec m, y = tgt m, the L1
 // and mask sums, its own pixels' dI/dflow and the A basis) and hands each row's
@@ -453,14 +354,8 @@ struct Consumer : PairCommon<BORDER, GRAD, C> {
   }
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
-  return v;
-}
-
-// The strip stream of one scale's workgroup blk of nblk (photo_pc_kernel: the
-// whole grid; photo_pyr_kernel: that scale's range of a multi-scale grid).
+// The strip stream of one scale's workgroup blk of nblk (that scale's range of
+// photo_fwd_kernel's grid).
 template <bool BORDER, bool GRAD, int C>
 __device__ __forceinline__ void pc_body(const StripArgs& a, float* __restrict__ partials, int blk, int nblk) {
   __shared__ float lds[kPairs][2][kRing * C * 2 * 64];  // [pair][x,y | gradient state]
@@ -571,16 +466,9 @@ __device__ __forceinline__ void pc_body(const StripArgs& a, float* __restrict__ 
   }
 }
 
-template <bool BORDER, bool GRAD, int C>
-__global__ __launch_bounds__(128 * kPairs) __attribute__((amdgpu_waves_per_eu(USF_PHOTO_EU))) void photo_pc_kernel(StripArgs a, float* __restrict__ partials) {
-  pc_body<BORDER, GRAD, C>(a, partials, blockIdx.x, gridDim.x);
-}
-
-// The loss scales of a with_bk step in ONE launch (usf_photo_loss_pyramid_fwd_f32):
-// scale s owns workgroups [start[s], start[s + 1]) -- the largest scale first,
-// so the small scales' few strips fill the chip's tail instead of each paying a
-// launch and a drain of their own.
-constexpr int kMaxScales = 4;
+// One launch for 1..4 scales (a single scale for the one-direction and pair
+// entries, the loss scales of a with_bk step for usf_photo_loss_pyramid_fwd_f32):
+// scale s owns workgroups [start[s], start[s + 1]) (strip.h).
 struct StripPyr {
   StripArgs sc[kMaxScales];
   float* part[kMaxScales];
@@ -588,28 +476,28 @@ struct StripPyr {
 };
 
 template <bool BORDER, bool GRAD, int C>
-__global__ __launch_bounds__(128 * kPairs) __attribute__((amdgpu_waves_per_eu(USF_PHOTO_EU))) void photo_pyr_kernel(StripPyr m) {
+__global__ __launch_bounds__(128 * kPairs) __attribute__((amdgpu_waves_per_eu(USF_PHOTO_EU))) void photo_fwd_kernel(StripPyr m) {
   const int blk = blockIdx.x;
-  const int s = (blk >= m.start[1]) + (blk >= m.start[2]) + (blk >= m.start[3]);  // unused scales: start = total
+  const int s = strip_scale(m.start, blk);
   pc_body<BORDER, GRAD, C>(m.sc[s], m.part[s], blk - m.start[s], m.start[s + 1] - m.start[s]);
 }
 
-// One block per (direction, scale): photo_final_kernel's fixed-order reduction.
+// One block per (direction, scale): fixed-order fp64 sum of its partials ->
+// out[3 (ndir s + dir) ..] = {loss, c_l1, c_ssim}, c_* = w_* / (N_* * (mean(m) + 1e-6)).
+constexpr int kFinNT = 512;
 struct FinPyr {
   const float* part[kMaxScales];
   int nblk[kMaxScales];
   double n1[kMaxScales], n2[kMaxScales], n3[kMaxScales];
 };
-__global__ __launch_bounds__(kFinNT) void photo_pyr_final_kernel(FinPyr f, float* __restrict__ out, float w_l1,
-                                                                 float w_ssim) {
-  const int s = blockIdx.y;
-  // the same code as the single-scale reduction, on this scale's partials (one
-  // block per direction: blockIdx.x) and outputs out[6 s ..]
+__global__ __launch_bounds__(kFinNT) void photo_final_kernel(FinPyr f, float* __restrict__ out, float w_l1,
+                                                             float w_ssim) {
   __shared__ double red[3][kFinNT / 64];
-  const int t = threadIdx.x, dirn = blockIdx.x, nblk = f.nblk[s];
+  const int t = threadIdx.x, dirn = blockIdx.x, s = blockIdx.y, nblk = f.nblk[s];
   const float* p = f.part[s] + (size_t)3 * nblk * dirn;
   double a = 0, b = 0, c = 0;
   int i = t;
+  // 4 slots in flight per thread, summed in slot order (fixed)
   for (; i + 3 * kFinNT < nblk; i += 4 * kFinNT) {
     float v[4][3];
 #pragma unroll
@@ -650,29 +538,32 @@ __global__ __launch_bounds__(kFinNT) void photo_pyr_final_kernel(FinPyr f, float
     const double n1 = f.n1[s], n2 = f.n2[s], n3 = f.n3[s];
     const double den = s2 / n3 + 1e-6;
     const double l1 = n1 > 0 ? s0 / n1 : 0.0, ss = n2 > 0 ? s1 / n2 : 0.0;
-    float* o = out + 6 * s + 3 * dirn;
+    float* o = out + 3 * ((size_t)gridDim.x * s + dirn);
     o[0] = (float)((w_l1 * l1 + w_ssim * ss) / den);
     o[1] = n1 > 0 ? (float)(w_l1 / (n1 * den)) : 0.f;
     o[2] = n2 > 0 ? (float)(w_ssim / (n2 * den)) : 0.f;
   }
 }
 
-// The backward of every scale in one launch: blockIdx.z = 2 s + direction.
+// --------------------------------------------------------------- backward --
+// gflow[b, 2 dir + j, p] = g_dir (c_l1 basis[b, 4 dir + j, p] + c_ssim basis[b, 4 dir + 2 + j, p])
+// for every scale in one launch: blockIdx.z = ndir s + direction (ndir = 1 or 2).
 struct BwdPyr {
   const float* basis[kMaxScales];
   float* gflow[kMaxScales];
   int HW[kMaxScales];
 };
-__global__ __launch_bounds__(256) void photo_pyr_bwd_kernel(BwdPyr m, const float* __restrict__ coef,
-                                                            const float* __restrict__ gloss) {
-  const int s = blockIdx.z >> 1, dirn = blockIdx.z & 1, b = blockIdx.y;
+__global__ __launch_bounds__(256) void photo_bwd_kernel(BwdPyr m, const float* __restrict__ coef,
+                                                        const float* __restrict__ gloss, int ndir) {
+  const int z = blockIdx.z, b = blockIdx.y;
+  const int s = ndir == 2 ? z >> 1 : z, dirn = ndir == 2 ? z & 1 : 0;  // no integer division
   const int HW = m.HW[s];
   const int i = (blockIdx.x * 256 + threadIdx.x) * 4;
   if (i >= HW) return;
-  const float gl = gloss[2 * s + dirn];
-  const float k1 = coef[6 * s + 3 * dirn + 1] * gl, k2 = coef[6 * s + 3 * dirn + 2] * gl;
-  const float* a = m.basis[s] + ((size_t)b * 2 + dirn) * 4 * HW;
-  float* o = m.gflow[s] + ((size_t)b * 2 + dirn) * 2 * HW;
+  const float gl = gloss[z];
+  const float k1 = coef[3 * z + 1] * gl, k2 = coef[3 * z + 2] * gl;
+  const float* a = m.basis[s] + ((size_t)b * ndir + dirn) * 4 * HW;
+  float* o = m.gflow[s] + ((size_t)b * ndir + dirn) * 2 * HW;
   if ((HW & 3) == 0) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -695,8 +586,6 @@ __global__ __launch_bounds__(256) void photo_pyr_bwd_kernel(BwdPyr m, const floa
 // profiles/r03_photo_rows.json), so below one wave per SIMD fewer, taller
 // strips do not help. The strips of a column are balanced (heights differ by
 // at most one row); the cheapest count wins, ties to fewer strips.
-constexpr int kSimds = 1024;  // 256 CUs x 4 SIMDs
-constexpr int kMinStripRows = 4;  // the partials buffer holds ceil(H / 4) strips per column
 constexpr long long kPairSlots = (long long)USF_PHOTO_EU * kSimds / 2;  // resident strips
 
 struct StripPlan {
@@ -726,17 +615,6 @@ StripPlan strip_plan(int B, int H, int W, int ndir) {
   return best;
 }
 
-template <bool BORDER, bool GRAD>
-hipError_t pc_launch_c(const StripArgs& sa, int C, dim3 grid, float* partials, hipStream_t s) {
-  if (C == 3)
-    hipLaunchKernelGGL((photo_pc_kernel<BORDER, GRAD, 3>), grid, dim3(128 * kPairs), 0, s, sa, partials);
-  else if (C == 2)
-    hipLaunchKernelGGL((photo_pc_kernel<BORDER, GRAD, 2>), grid, dim3(128 * kPairs), 0, s, sa, partials);
-  else
-    hipLaunchKernelGGL((photo_pc_kernel<BORDER, GRAD, 1>), grid, dim3(128 * kPairs), 0, s, sa, partials);
-  return hipGetLastError();
-}
-
 // StripArgs of one launch (one scale, ndir directions) and its workgroup count.
 StripArgs strip_args(const PhotoArgs& a, int ndir, unsigned& nwg) {
   StripArgs sa{};
@@ -759,85 +637,109 @@ StripArgs strip_args(const PhotoArgs& a, int ndir, unsigned& nwg) {
 }
 
 template <bool BORDER, bool GRAD>
-hipError_t pyr_launch_c(const StripPyr& m, int C, dim3 grid, hipStream_t s) {
+hipError_t fwd_launch_c(const StripPyr& m, int C, dim3 grid, hipStream_t s) {
   if (C == 3)
-    hipLaunchKernelGGL((photo_pyr_kernel<BORDER, GRAD, 3>), grid, dim3(128 * kPairs), 0, s, m);
+    hipLaunchKernelGGL((photo_fwd_kernel<BORDER, GRAD, 3>), grid, dim3(128 * kPairs), 0, s, m);
   else if (C == 2)
-    hipLaunchKernelGGL((photo_pyr_kernel<BORDER, GRAD, 2>), grid, dim3(128 * kPairs), 0, s, m);
+    hipLaunchKernelGGL((photo_fwd_kernel<BORDER, GRAD, 2>), grid, dim3(128 * kPairs), 0, s, m);
   else
-    hipLaunchKernelGGL((photo_pyr_kernel<BORDER, GRAD, 1>), grid, dim3(128 * kPairs), 0, s, m);
+    hipLaunchKernelGGL((photo_fwd_kernel<BORDER, GRAD, 1>), grid, dim3(128 * kPairs), 0, s, m);
   return hipGetLastError();
 }
 
-hipError_t photo_launch(const PhotoArgs& a, int ndir, int pad_mode, float* partials, float* out,
-                              float w_l1, float w_ssim, hipStream_t s) {
-  StripArgs sa{};
-  sa.dir[0] = a.dir[0];
-  sa.dir[1] = a.dir[1];
-  sa.fbs = a.fbs;
-  sa.bbs = a.bbs;
-  sa.B = a.B;
-  sa.H = a.H;
-  sa.W = a.W;
-  const StripPlan plan = strip_plan(a.B, a.H, a.W, ndir);
-  sa.R = plan.R;
-  sa.nsx = (a.W + kSO - 1) / kSO;
-  sa.nsy = plan.nsy;
-  sa.ndir = ndir;
-  sa.nitems = ndir * a.B * sa.nsx * sa.nsy;
-  const bool grad = a.dir[0].basis != nullptr;
-  // a producer / consumer pair of waves per strip, two strips per workgroup
-  const int npx = kPairs == 1 ? ndir * sa.nsx : ndir == 2 ? sa.nsx : (sa.nsx + 1) / 2;
-  const dim3 grid((unsigned)(a.B * sa.nsy * npx));
+struct Scale {
+  PhotoDir dir[2];
+  long long fbs, bbs;
+  int H, W;
+};
+
+// The strips of nscale scales, ndir directions each, in one launch, then one
+// final block per (direction, scale). Every scale runs the same code on the
+// same strips whichever entry launched it (the strip heights depend on ndir,
+// strip_plan, not on the other scales), so the pyramid's numbers are the
+// per-scale pair calls' bit for bit.
+hipError_t photo_launch(int nscale, const Scale* sc, int ndir, int B, int C, int pad_mode, float* partials,
+                        float* out, float w_l1, float w_ssim, hipStream_t s) {
+  StripPyr m{};
+  FinPyr f{};
+  bool grad = false;
+  unsigned total = 0;
+  long long poff = 0;
+  for (int k = 0; k < nscale; ++k) {
+    PhotoArgs a{};
+    a.dir[0] = sc[k].dir[0];
+    a.dir[1] = sc[k].dir[ndir - 1];
+    a.fbs = sc[k].fbs;
+    a.bbs = sc[k].bbs;
+    a.B = B; a.C = C; a.H = sc[k].H; a.W = sc[k].W;
+    grad = grad || a.dir[0].basis != nullptr;
+    unsigned nwg = 0;
+    m.sc[k] = strip_args(a, ndir, nwg);
+    m.part[k] = partials + poff;
+    m.start[k] = (int)total;
+    total += nwg;
+    f.part[k] = partials + poff;
+    f.nblk[k] = B * m.sc[k].nsx * m.sc[k].nsy;
+    f.n1[k] = (double)B * C * a.H * a.W;
+    f.n2[k] = (a.H >= 3 && a.W >= 3) ? (double)B * C * (a.H - 2) * (a.W - 2) : 0.0;
+    f.n3[k] = (double)B * a.H * a.W;
+    poff += (long long)ndir * photo_partials(B, a.H, a.W);
+  }
+  strip_pad_scales(m, nscale, total);
   hipError_t e;
+  const dim3 grid(total);
   if (pad_mode == 1)
-    e = grad ? pc_launch_c<true, true>(sa, a.C, grid, partials, s) : pc_launch_c<true, false>(sa, a.C, grid, partials, s);
+    e = grad ? fwd_launch_c<true, true>(m, C, grid, s) : fwd_launch_c<true, false>(m, C, grid, s);
   else
-    e = grad ? pc_launch_c<false, true>(sa, a.C, grid, partials, s) : pc_launch_c<false, false>(sa, a.C, grid, partials, s);
+    e = grad ? fwd_launch_c<false, true>(m, C, grid, s) : fwd_launch_c<false, false>(m, C, grid, s);
   if (e != hipSuccess) return e;
-  const double n1 = (double)a.B * a.C * a.H * a.W;
-  const double n2 = (a.H >= 3 && a.W >= 3) ? (double)a.B * a.C * (a.H - 2) * (a.W - 2) : 0.0;
-  const double n3 = (double)a.B * a.H * a.W;
-  hipLaunchKernelGGL(photo_final_kernel, dim3((unsigned)ndir), dim3(kFinNT), 0, s, partials,
-                     a.B * sa.nsx * sa.nsy, out, n1, n2, n3, w_l1, w_ssim);
+  hipLaunchKernelGGL(photo_final_kernel, dim3((unsigned)ndir, (unsigned)nscale), dim3(kFinNT), 0, s, f, out, w_l1,
+                     w_ssim);
   return hipGetLastError();
+}
+
+// both directions of a with_bk scale: dir 0 warps im2 by flow[:, 0:2] onto im1
+// (mask1), dir 1 warps im1 by flow[:, 2:4] onto im2 (mask2) (flow_loss.py:130-131).
+// basis: [B, 2, 4, H, W] (= [B,8,H,W]) or null; the basis block of (sample b,
+// direction d) is at basis + (2 b + d) * 4HW.
+Scale pair_scale(const float* im1, const float* im2, const float* mask1, const float* mask2, const float* flow,
+                 long long fbs, float* basis, int H, int W) {
+  Scale sc{};
+  const size_t HW = (size_t)H * W;
+  sc.dir[0] = PhotoDir{im2, im1, mask1, flow, basis};
+  sc.dir[1] = PhotoDir{im1, im2, mask2, flow + 2 * HW, basis ? basis + 4 * HW : nullptr};
+  sc.fbs = fbs;
+  sc.bbs = 8LL * H * W;
+  sc.H = H;
+  sc.W = W;
+  return sc;
 }
 
 }  // namespace
 
 int photo_partials(int B, int H, int W) {
-  // any strip height (the smallest R has the most strips)
+  // any strip height (the smallest R has the most strips), per direction
   return 3 * B * ((H + kMinStripRows - 1) / kMinStripRows) * ((W + kSO - 1) / kSO);
 }
 
 hipError_t photo_fwd_launch(const float* src, const float* tgt, const float* mask, const float* flow,
                             long long fbs, float* partials, float* out, float* basis, int B, int C,
                             int H, int W, int pad_mode, float w_l1, float w_ssim, hipStream_t s) {
-  PhotoArgs a{};
-  a.dir[0] = PhotoDir{src, tgt, mask, flow, basis};
-  a.dir[1] = a.dir[0];
-  a.fbs = fbs;
-  a.bbs = 4LL * H * W;
-  a.B = B; a.C = C; a.H = H; a.W = W;
-  return photo_launch(a, 1, pad_mode, partials, out, w_l1, w_ssim, s);
+  Scale sc{};
+  sc.dir[0] = PhotoDir{src, tgt, mask, flow, basis};
+  sc.fbs = fbs;
+  sc.bbs = 4LL * H * W;
+  sc.H = H;
+  sc.W = W;
+  return photo_launch(1, &sc, 1, B, C, pad_mode, partials, out, w_l1, w_ssim, s);
 }
 
-// both directions of a with_bk scale: dir 0 warps im2 by flow[:, 0:2] onto im1
-// (mask1), dir 1 warps im1 by flow[:, 2:4] onto im2 (mask2) (flow_loss.py:130-131).
-// basis: [B, 2, 4, H, W] (= [B,8,H,W]) or null.
 hipError_t photo_pair_fwd_launch(const float* im1, const float* im2, const float* mask1,
                                  const float* mask2, const float* flow, long long fbs,
                                  float* partials, float* out, float* basis, int B, int C, int H,
                                  int W, int pad_mode, float w_l1, float w_ssim, hipStream_t s) {
-  PhotoArgs a{};
-  const size_t HW = (size_t)H * W;
-  // basis block of (sample b, direction d) at basis + (2 b + d) * 4HW
-  a.dir[0] = PhotoDir{im2, im1, mask1, flow, basis};
-  a.dir[1] = PhotoDir{im1, im2, mask2, flow + 2 * HW, basis ? basis + 4 * HW : nullptr};
-  a.fbs = fbs;
-  a.bbs = 8LL * H * W;
-  a.B = B; a.C = C; a.H = H; a.W = W;
-  return photo_launch(a, 2, pad_mode, partials, out, w_l1, w_ssim, s);
+  const Scale sc = pair_scale(im1, im2, mask1, mask2, flow, fbs, basis, H, W);
+  return photo_launch(1, &sc, 2, B, C, pad_mode, partials, out, w_l1, w_ssim, s);
 }
 
 hipError_t photo_pyr_fwd_launch(int nscale, const float* const* im1, const float* const* im2,
@@ -846,48 +748,14 @@ hipError_t photo_pyr_fwd_launch(int nscale, const float* const* im1, const float
                                 float* const* basis, int B, int C, int pad_mode, float w_l1, float w_ssim,
                                 hipStream_t s) {
   if (nscale < 1 || nscale > kMaxScales) return hipErrorInvalidValue;
-  StripPyr m{};
-  FinPyr f{};
-  bool grad = false;
-  unsigned total = 0;
-  long long poff = 0;
-  for (int k = 0; k < nscale; ++k) {
-    PhotoArgs a{};
-    const size_t HW = (size_t)H[k] * W[k];
-    float* bk = basis ? basis[k] : nullptr;
-    a.dir[0] = PhotoDir{im2[k], im1[k], mask1[k], flow[k], bk};
-    a.dir[1] = PhotoDir{im1[k], im2[k], mask2[k], flow[k] + 2 * HW, bk ? bk + 4 * HW : nullptr};
-    a.fbs = fbs[k];
-    a.bbs = 8LL * H[k] * W[k];
-    a.B = B; a.C = C; a.H = H[k]; a.W = W[k];
-    grad = grad || bk != nullptr;
-    unsigned nwg = 0;
-    m.sc[k] = strip_args(a, 2, nwg);
-    m.part[k] = partials + poff;
-    m.start[k] = (int)total;
-    total += nwg;
-    f.part[k] = partials + poff;
-    f.nblk[k] = B * m.sc[k].nsx * m.sc[k].nsy;
-    f.n1[k] = (double)B * C * H[k] * W[k];
-    f.n2[k] = (H[k] >= 3 && W[k] >= 3) ? (double)B * C * (H[k] - 2) * (W[k] - 2) : 0.0;
-    f.n3[k] = (double)B * H[k] * W[k];
-    poff += 2LL * photo_partials(B, H[k], W[k]);
-  }
-  for (int k = nscale; k <= kMaxScales; ++k) m.start[k] = (int)total;
-  for (int k = nscale; k < kMaxScales; ++k) m.sc[k] = m.sc[0];  // never selected (start[k] = total)
-  hipError_t e;
-  const dim3 grid(total);
-  if (pad_mode == 1)
-    e = grad ? pyr_launch_c<true, true>(m, C, grid, s) : pyr_launch_c<true, false>(m, C, grid, s);
-  else
-    e = grad ? pyr_launch_c<false, true>(m, C, grid, s) : pyr_launch_c<false, false>(m, C, grid, s);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(photo_pyr_final_kernel, dim3(2, (unsigned)nscale), dim3(kFinNT), 0, s, f, out, w_l1, w_ssim);
-  return hipGetLastError();
+  Scale sc[kMaxScales];
+  for (int k = 0; k < nscale; ++k)
+    sc[k] = pair_scale(im1[k], im2[k], mask1[k], mask2[k], flow[k], fbs[k], basis ? basis[k] : nullptr, H[k], W[k]);
+  return photo_launch(nscale, sc, 2, B, C, pad_mode, partials, out, w_l1, w_ssim, s);
 }
 
 hipError_t photo_pyr_bwd_launch(int nscale, const float* const* basis, const float* coef, const float* gloss,
-                                float* const* gflow, const int* H, const int* W, int B, hipStream_t s) {
+                                float* const* gflow, const int* H, const int* W, int B, int ndir, hipStream_t s) {
   if (nscale < 1 || nscale > kMaxScales) return hipErrorInvalidValue;
   BwdPyr m{};
   int hwmax = 0;
@@ -897,17 +765,10 @@ hipError_t photo_pyr_bwd_launch(int nscale, const float* const* basis, const flo
     m.HW[k] = H[k] * W[k];
     hwmax = std::max(hwmax, m.HW[k]);
   }
-  const dim3 grid((unsigned)((hwmax + 1023) / 1024), (unsigned)B, (unsigned)(2 * nscale));
-  hipLaunchKernelGGL(photo_pyr_bwd_kernel, grid, dim3(256), 0, s, m, coef, gloss);
-  return hipGetLastError();
-}
-
-hipError_t photo_bwd_launch(const float* basis, const float* coef, const float* gloss, float* gflow,
-                            int B, int H, int W, int ndir, hipStream_t s) {
-  const int HW = H * W;
-  const dim3 grid((unsigned)((HW + 1023) / 1024), (unsigned)B, (unsigned)ndir);
-  hipLaunchKernelGGL(photo_bwd_kernel, grid, dim3(256), 0, s, basis, coef, gloss, gflow, HW, ndir);
+  const dim3 grid((unsigned)((hwmax + 1023) / 1024), (unsigned)B, (unsigned)(ndir * nscale));
+  hipLaunchKernelGGL(photo_bwd_kernel, grid, dim3(256), 0, s, m, coef, gloss, ndir);
   return hipGetLastError();
 }
 
 }  // namespace usf
+

@@ -131,6 +131,7 @@ hipError_t occ_backward_persist_launch(const float* flow, long long flow_bstride
 hipError_t occ_bidirection_launch(const float* flow12, long long bs12, const float* flow21, long long bs21,
                                   float* occ, int B, int H, int W, float scale, float bias, hipStream_t s);
 
+// photo.hip: the L1 + SSIM photometric term; partials per direction
 int photo_partials(int B, int H, int W);
 hipError_t photo_fwd_launch(const float* src, const float* tgt, const float* mask, const float* flow,
                             long long flow_bstride, float* partials, float* out, float* basis, int B,
@@ -144,10 +145,9 @@ hipError_t photo_pyr_fwd_launch(int nscale, const float* const* im1, const float
                                 const long long* fbs, const int* H, const int* W, float* partials, float* out,
                                 float* const* basis, int B, int C, int pad_mode, float w_l1, float w_ssim,
                                 hipStream_t s);
+// every scale's [B, 4 ndir, H, W] basis -> [B, 2 ndir, H, W] gradient in one launch (ndir = 1 or 2)
 hipError_t photo_pyr_bwd_launch(int nscale, const float* const* basis, const float* coef, const float* gloss,
-                                float* const* gflow, const int* H, const int* W, int B, hipStream_t s);
-hipError_t photo_bwd_launch(const float* basis, const float* coef, const float* gloss, float* gflow,
-                            int B, int H, int W, int ndir, hipStream_t s);
+                                float* const* gflow, const int* H, const int* W, int B, int ndir, hipStream_t s);
 
 // census.hip: the ternary (census) photometric term; partials per direction
 int census_partials(int B, int H, int W);

@@ -7,9 +7,11 @@ CPU path: CPU tensors raise ``RuntimeError``.
 """
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 from . import _lib
 from . import kernel_timer as _kt
@@ -387,7 +389,41 @@ def occ_bidirection(flow12: torch.Tensor, flow21: torch.Tensor, scale: float = 0
     return out
 
 
-def _photo_args(src, tgt, mask, flow):
+def _host_array(ctype, values):
+    return (ctype * len(values))(*values)
+
+
+# ---- the fused photometric losses: L1 + SSIM (photo.hip) and census (census.hip).
+# Both families have the same six entries with the same arguments. A _LossKind
+# holds what differs: the prefix of the usf_<prefix>_loss_* entries and of the
+# <prefix>_* timer ops, the title of the messages, the floats of out per
+# direction (the loss, then its coefficients), the planes of the gradient basis
+# per direction, the entries' weight arguments, and the channel / shape rule
+# (census: C = 3 and an interior pixel; else C <= 3). The _loss_* functions bind
+# each entry once.
+_LossKind = namedtuple("_LossKind", "prefix title nout planes weights census_rule")
+_PHOTO = _LossKind("photo", "photometric", 3, 4, ("w_l1", "w_ssim"), False)
+_CENSUS = _LossKind("census", "census", 2, 2, ("w_ternary",), True)
+
+
+def _loss_call(kind, entry, op, key, device, nbytes, args):
+    name = f"usf_{kind.prefix}_loss_{entry}"
+    fn, stream = getattr(_lib.load(), name), _lib.stream_handle(device)
+    with torch.cuda.device(device), _kt.timed(f"{kind.prefix}_{op}", key, device, nbytes):
+        rc = fn(*args, stream)
+    _lib.check(rc, name)
+
+
+def _loss_tail(kind, pad, weights):
+    """(pad_mode, *weights), the last arguments of a forward entry."""
+    if pad not in PAD_MODES:
+        raise NotImplementedError(f"flow_warp padding mode {pad!r} (supported: border, zeros)")
+    if len(weights) != len(kind.weights):
+        raise TypeError(f"the {kind.title} loss takes the weights {kind.weights}, got {len(weights)} values")
+    return (PAD_MODES[pad],) + tuple(float(w) for w in weights)
+
+
+def _loss_images(kind, src, tgt, mask):
     for n, t in (("src", src), ("tgt", tgt), ("mask", mask)):
         _require_device_f32(n, t)
     B, C, H, W = _nchw("src", src)
@@ -395,217 +431,15 @@ def _photo_args(src, tgt, mask, flow):
         raise ValueError(f"tgt {tuple(tgt.shape)} / mask {tuple(mask.shape)} do not match src {(B, C, H, W)}")
     if C > 3:
         raise NotImplementedError(f"fused photometric loss supports C <= 3 image channels, got {C}")
-    if flow is None:
-        return src.contiguous(), tgt.contiguous(), mask.contiguous(), B, C, H, W
-    _require_device_f32("flow", flow)
-    fv, fbs = _flow_view(flow, B, H, W)
-    return src.contiguous(), tgt.contiguous(), mask.contiguous(), fv, fbs, B, C, H, W
-
-
-def photo_loss_forward(src, tgt, mask, flow, pad: str = "border", w_l1: float = 0.15, w_ssim: float = 0.85,
-                       need_grad: bool = False):
-    """Fused warp + occlusion-aware L1/SSIM photometric loss of one scale and
-    direction (flow_loss.py:127-148, loss_blocks.py:53-72) -> (out, basis):
-    ``out`` = tensor [3] on the device {loss, c_l1, c_ssim}; with ``need_grad``
-    ``basis`` = [B,4,H,W], the per-pixel flow-gradient basis computed in the
-    same pass (dL/dflow = c_l1 * basis[:, :2] + c_ssim * basis[:, 2:]), else None."""
-    if pad not in PAD_MODES:
-        raise NotImplementedError(f"flow_warp padding mode {pad!r} (supported: border, zeros)")
-    s, t, m, fv, fbs, B, C, H, W = _photo_args(src, tgt, mask, flow)
-    lib = _lib.load()
-    partials = torch.empty(lib.usf_photo_loss_partials(B, H, W), device=src.device, dtype=torch.float32)
-    out = torch.empty(3, device=src.device, dtype=torch.float32)
-    basis = torch.empty((B, 4, H, W), device=src.device, dtype=torch.float32) if need_grad else None
-    # algorithmic bytes: src, tgt, mask, flow read once; the basis written once
-    nbytes = 4 * B * H * W * (2 * C + 3 + (4 if need_grad else 0))
-    op = "photo_fwd_grad" if need_grad else "photo_fwd"
-    _args = (s.data_ptr(), t.data_ptr(), m.data_ptr(), fv.data_ptr(), fbs, partials.data_ptr(), out.data_ptr(),
-             basis.data_ptr() if need_grad else None, B, C, H, W, PAD_MODES[pad], float(w_l1), float(w_ssim),
-             _lib.stream_handle(src.device),)
-    with torch.cuda.device(src.device), _kt.timed(op, (B, C, H, W, pad), src.device, nbytes):
-        rc = lib.usf_photo_loss_fwd_f32(*_args)
-    _lib.check(rc, "usf_photo_loss_fwd_f32")
-    return out, basis
-
-
-def photo_loss_pair_forward(flow, im1, im2, mask1, mask2, pad: str = "border", w_l1: float = 0.15,
-                            w_ssim: float = 0.85, need_grad: bool = False):
-    """Both directions of a with_bk scale in one launch (flow_loss.py:130-131):
-    direction 0 = loss(im1, warp(im2, flow[:, :2]), mask1), direction 1 =
-    loss(im2, warp(im1, flow[:, 2:]), mask2) -> (out [6] = {loss, c_l1, c_ssim}
-    per direction, basis [B,8,H,W] (= [B,2,4,H,W]) or None)."""
-    if pad not in PAD_MODES:
-        raise NotImplementedError(f"flow_warp padding mode {pad!r} (supported: border, zeros)")
-    a, b_, m1, B, C, H, W = _photo_args(im1, im2, mask1, None)
-    m2 = mask2.contiguous()
-    _require_device_f32("mask2", m2)
-    if tuple(m2.shape) != (B, 1, H, W):
-        raise ValueError(f"mask2 {tuple(m2.shape)} does not match {(B, 1, H, W)}")
-    _require_device_f32("flow", flow)
-    if tuple(flow.shape) != (B, 4, H, W):
-        raise ValueError(f"flow must be [B,4,H,W] = {(B, 4, H, W)}, got {tuple(flow.shape)}")
-    fv = flow if flow[0].is_contiguous() else flow.contiguous()
-    fbs = fv.stride(0) if B > 1 else 4 * H * W
-    lib = _lib.load()
-    partials = torch.empty(2 * lib.usf_photo_loss_partials(B, H, W), device=im1.device, dtype=torch.float32)
-    out = torch.empty(6, device=im1.device, dtype=torch.float32)
-    basis = torch.empty((B, 8, H, W), device=im1.device, dtype=torch.float32) if need_grad else None
-    # algorithmic bytes (SURVEY 8d, each input read once): im1 and im2 (2C), the
-    # 4-channel flow, both masks; with the gradient the 8 basis planes written once
-    nbytes = 4 * B * H * W * (2 * C + 4 + 2 + (8 if need_grad else 0))
-    op = "photo_pair_grad" if need_grad else "photo_pair"
-    _args = (a.data_ptr(), b_.data_ptr(), m1.data_ptr(), m2.data_ptr(), fv.data_ptr(), fbs, partials.data_ptr(),
-             out.data_ptr(), basis.data_ptr() if need_grad else None, B, C, H, W, PAD_MODES[pad], float(w_l1),
-             float(w_ssim), _lib.stream_handle(im1.device),)
-    with torch.cuda.device(im1.device), _kt.timed(op, (B, C, H, W, pad), im1.device, nbytes):
-        rc = lib.usf_photo_loss_pair_fwd_f32(*_args)
-    _lib.check(rc, "usf_photo_loss_pair_fwd_f32")
-    return out, basis
-
-
-def _host_array(ctype, values):
-    return (ctype * len(values))(*values)
-
-
-def photo_loss_pyramid_forward(flows, im1s, im2s, masks1, masks2, pad: str = "border", w_l1: float = 0.15,
-                               w_ssim: float = 0.85, need_grad: bool = False):
-    """:func:`photo_loss_pair_forward` for up to 4 loss scales in one launch
-    (usf_photo_loss_pyramid_fwd_f32; the largest scale first) -> (out
-    [nscale, 6] = {loss, c_l1, c_ssim} per direction per scale, bases: a list
-    of [B,8,H_k,W_k] or None)."""
-    import ctypes
-
-    if pad not in PAD_MODES:
-        raise NotImplementedError(f"flow_warp padding mode {pad!r} (supported: border, zeros)")
-    n = len(flows)
-    if not 1 <= n <= 4 or not (len(im1s) == len(im2s) == len(masks1) == len(masks2) == n):
-        raise ValueError(f"1..4 scales with one flow, two images and two masks each (got {n})")
-    args = []
-    for f, a, b_, m1, m2 in zip(flows, im1s, im2s, masks1, masks2):
-        a, b_, m1, B, C, H, W = _photo_args(a, b_, m1, None)
-        m2 = m2.contiguous()
-        _require_device_f32("mask2", m2)
-        _require_device_f32("flow", f)
-        if tuple(m2.shape) != (B, 1, H, W) or tuple(f.shape) != (B, 4, H, W):
-            raise ValueError(f"scale {len(args)}: mask2 {tuple(m2.shape)} / flow {tuple(f.shape)} vs {(B, C, H, W)}")
-        fv = f if f[0].is_contiguous() else f.contiguous()
-        args.append((fv, a, b_, m1, m2, B, C, H, W, fv.stride(0) if B > 1 else 4 * H * W))
-    B, C = args[0][5], args[0][6]
-    if any(x[5] != B or x[6] != C for x in args):
-        raise ValueError("every scale needs the same batch and channel count")
-    dev = args[0][1].device
-    Hs = _host_array(ctypes.c_int, [x[7] for x in args])
-    Ws = _host_array(ctypes.c_int, [x[8] for x in args])
-    lib = _lib.load()
-    npart = int(lib.usf_photo_loss_pyramid_partials(n, Hs, Ws, B))
-    partials = torch.empty(npart, device=dev, dtype=torch.float32)
-    out = torch.empty((n, 6), device=dev, dtype=torch.float32)
-    bases = [torch.empty((B, 8, x[7], x[8]), device=dev, dtype=torch.float32) for x in args] if need_grad else None
-    ptrs = lambda i: _host_array(ctypes.c_void_p, [x[i].data_ptr() for x in args])  # noqa: E731
-    nbytes = sum(4 * B * x[7] * x[8] * (2 * C + 4 + 2 + (8 if need_grad else 0)) for x in args)
-    op = "photo_pyr_grad" if need_grad else "photo_pyr"
-    key = (B, C) + tuple(v for x in args for v in (x[7], x[8])) + (pad,)
-    _args = (n, ptrs(1), ptrs(2), ptrs(3), ptrs(4), ptrs(0), _host_array(ctypes.c_longlong, [x[9] for x in args]),
-             Hs, Ws, partials.data_ptr(), npart, out.data_ptr(),
-             _host_array(ctypes.c_void_p, [t.data_ptr() for t in bases]) if need_grad else None, B, C,
-             PAD_MODES[pad], float(w_l1), float(w_ssim), _lib.stream_handle(dev),)
-    with torch.cuda.device(dev), _kt.timed(op, key, dev, nbytes):
-        rc = lib.usf_photo_loss_pyramid_fwd_f32(*_args)
-    _lib.check(rc, "usf_photo_loss_pyramid_fwd_f32")
-    return out, bases
-
-
-def photo_loss_pyramid_backward(bases, coef, grad_losses):
-    """d(loss)/d(flow_k) * grad for every scale of :func:`photo_loss_pyramid_forward`
-    in one launch: bases [B,8,H_k,W_k], coef = its out [nscale, 6], grad_losses
-    [nscale, 2] -> list of [B,4,H_k,W_k] (deterministic)."""
-    import ctypes
-
-    n = len(bases)
-    for t in bases:
-        _require_device_f32("basis", t)
-    B = bases[0].shape[0]
-    dev = bases[0].device
-    gl = grad_losses.reshape(-1).to(torch.float32).contiguous()
-    if gl.numel() != 2 * n or coef.numel() != 6 * n:
-        raise ValueError(f"grad_losses / coef sizes {gl.numel()} / {coef.numel()} for {n} scales")
-    gflows = [torch.empty((B, 4) + tuple(t.shape[2:]), device=dev, dtype=torch.float32) for t in bases]
-    Hs = _host_array(ctypes.c_int, [t.shape[2] for t in bases])
-    Ws = _host_array(ctypes.c_int, [t.shape[3] for t in bases])
-    lib = _lib.load()
-    key = (B, 2) + tuple(v for t in bases for v in t.shape[2:])
-    nbytes = sum(4 * B * t.shape[2] * t.shape[3] * 12 for t in bases)
-    _args = (n, _host_array(ctypes.c_void_p, [t.contiguous().data_ptr() for t in bases]),
-             coef.contiguous().data_ptr(), gl.data_ptr(),
-             _host_array(ctypes.c_void_p, [t.data_ptr() for t in gflows]), Hs, Ws, B, _lib.stream_handle(dev),)
-    with torch.cuda.device(dev), _kt.timed("photo_pyr_bwd", key, dev, nbytes):
-        rc = lib.usf_photo_loss_pyramid_bwd_f32(*_args)
-    _lib.check(rc, "usf_photo_loss_pyramid_bwd_f32")
-    return gflows
-
-
-def photo_loss_backward(basis, coef, grad_loss):
-    """d(photo loss)/d(flow) * grad_loss from the forward's gradient basis
-    ([B,4,H,W] one direction, [B,8,H,W] a pair) and coefficients ->
-    [B,2,H,W] / [B,4,H,W] (deterministic)."""
-    _require_device_f32("basis", basis)
-    B, K, H, W = _nchw("basis", basis)
-    if K not in (4, 8):
-        raise ValueError(f"gradient basis must be [B,4,H,W] or [B,8,H,W], got {tuple(basis.shape)}")
-    ndir = K // 4
-    basis = basis.contiguous()
-    gl = grad_loss.reshape(-1).to(torch.float32).contiguous()
-    if gl.numel() != ndir:
-        raise ValueError(f"grad_loss has {gl.numel()} elements for {ndir} direction(s)")
-    gflow = torch.empty((B, 2 * ndir, H, W), device=basis.device, dtype=torch.float32)
-    lib = _lib.load()
-    _args = (basis.data_ptr(), coef.data_ptr(), gl.data_ptr(), gflow.data_ptr(), B, H, W, ndir,
-             _lib.stream_handle(basis.device),)
-    with torch.cuda.device(basis.device), _kt.timed("photo_bwd", (B, ndir, H, W), basis.device,
-                                                      4 * B * H * W * 6 * ndir):
-        rc = lib.usf_photo_loss_bwd_f32(*_args)
-    _lib.check(rc, "usf_photo_loss_bwd_f32")
-    return gflow
-
-
-def _census_args(src, tgt, mask, flow):
-    out = _photo_args(src, tgt, mask, flow)
-    C, H, W = out[-3:]
-    if C != 3:
+    if kind.census_rule and C != 3:
         raise NotImplementedError(f"fused census loss needs C = 3 image channels, got {C}")
-    if H < 3 or W < 3:
+    if kind.census_rule and (H < 3 or W < 3):
         raise ValueError(f"fused census loss needs H, W >= 3 (an interior pixel), got {(H, W)}")
-    return out
+    return src.contiguous(), tgt.contiguous(), mask.contiguous(), B, C, H, W
 
 
-def census_loss_forward(src, tgt, mask, flow, pad: str = "border", w_ternary: float = 1.0,
-                        need_grad: bool = False):
-    """Fused warp + occlusion-aware ternary (census) loss of one scale and
-    direction (flow_loss.py:127-148, loss_blocks.py:12-50) -> (out, basis):
-    ``out`` = tensor [2] on the device {loss, c_t}; with ``need_grad``
-    ``basis`` = [B,2,H,W], the per-pixel flow-gradient basis computed in the
-    same pass (dL/dflow = c_t * basis), else None."""
-    if pad not in PAD_MODES:
-        raise NotImplementedError(f"flow_warp padding mode {pad!r} (supported: border, zeros)")
-    s, t, m, fv, fbs, B, C, H, W = _census_args(src, tgt, mask, flow)
-    lib = _lib.load()
-    partials = torch.empty(lib.usf_census_loss_partials(B, H, W), device=src.device, dtype=torch.float32)
-    out = torch.empty(2, device=src.device, dtype=torch.float32)
-    basis = torch.empty((B, 2, H, W), device=src.device, dtype=torch.float32) if need_grad else None
-    # algorithmic bytes: src, tgt, mask, flow read once; the basis written once
-    nbytes = 4 * B * H * W * (2 * C + 3 + (2 if need_grad else 0))
-    op = "census_fwd_grad" if need_grad else "census_fwd"
-    _args = (s.data_ptr(), t.data_ptr(), m.data_ptr(), fv.data_ptr(), fbs, partials.data_ptr(), out.data_ptr(),
-             basis.data_ptr() if need_grad else None, B, C, H, W, PAD_MODES[pad], float(w_ternary),
-             _lib.stream_handle(src.device),)
-    with torch.cuda.device(src.device), _kt.timed(op, (B, C, H, W, pad), src.device, nbytes):
-        rc = lib.usf_census_loss_fwd_f32(*_args)
-    _lib.check(rc, "usf_census_loss_fwd_f32")
-    return out, basis
-
-
-def _census_pair_args(flow, im1, im2, mask1, mask2):
-    a, b_, m1, B, C, H, W = _census_args(im1, im2, mask1, None)
+def _loss_pair_args(kind, flow, im1, im2, mask1, mask2):
+    a, b_, m1, B, C, H, W = _loss_images(kind, im1, im2, mask1)
     m2 = mask2.contiguous()
     _require_device_f32("mask2", m2)
     _require_device_f32("flow", flow)
@@ -617,126 +451,175 @@ def _census_pair_args(flow, im1, im2, mask1, mask2):
     return fv, a, b_, m1, m2, B, C, H, W, fv.stride(0) if B > 1 else 4 * H * W
 
 
-def census_loss_pair_forward(flow, im1, im2, mask1, mask2, pad: str = "border", w_ternary: float = 1.0,
-                             need_grad: bool = False):
+def _loss_forward(kind, ndir, flow, a, b_, m1, m2, pad, weights, need_grad):
+    """One scale. ndir = 1: rec = warp(a, flow [B,2,H,W]) against b_ under m1 (m2
+    unused); ndir = 2: the with_bk pair of im1 = a, im2 = b_ and flow [B,4,H,W]."""
+    tail = _loss_tail(kind, pad, weights)
+    if ndir == 2:
+        fv, a, b_, m1, m2, B, C, H, W, fbs = _loss_pair_args(kind, flow, a, b_, m1, m2)
+        masks, entry, op = (m1.data_ptr(), m2.data_ptr()), "pair_fwd_f32", "pair"
+    else:
+        a, b_, m1, B, C, H, W = _loss_images(kind, a, b_, m1)
+        _require_device_f32("flow", flow)
+        fv, fbs = _flow_view(flow, B, H, W)
+        masks, entry, op = (m1.data_ptr(),), "fwd_f32", "fwd"
+    dev = a.device
+    npart = ndir * getattr(_lib.load(), f"usf_{kind.prefix}_loss_partials")(B, H, W)
+    partials = torch.empty(npart, device=dev, dtype=torch.float32)
+    out = torch.empty(ndir * kind.nout, device=dev, dtype=torch.float32)
+    basis = torch.empty((B, ndir * kind.planes, H, W), device=dev, dtype=torch.float32) if need_grad else None
+    # algorithmic bytes (SURVEY 8d, each input read once): both images (2C), per
+    # direction its flow and mask; with the gradient the basis planes written once
+    nbytes = 4 * B * H * W * (2 * C + 3 * ndir + (ndir * kind.planes if need_grad else 0))
+    _loss_call(kind, entry, op + ("_grad" if need_grad else ""), (B, C, H, W, pad), dev, nbytes,
+               (a.data_ptr(), b_.data_ptr()) + masks + (fv.data_ptr(), fbs, partials.data_ptr(), out.data_ptr(),
+                                                        _ptr(basis), B, C, H, W) + tail)
+    return out, basis
+
+
+def _loss_pyramid_forward(kind, flows, im1s, im2s, masks1, masks2, pad, weights, need_grad):
+    tail = _loss_tail(kind, pad, weights)
+    n = len(flows)
+    if not 1 <= n <= 4 or not (len(im1s) == len(im2s) == len(masks1) == len(masks2) == n):
+        raise ValueError(f"1..4 scales with one flow, two images and two masks each (got {n})")
+    args = [_loss_pair_args(kind, *x) for x in zip(flows, im1s, im2s, masks1, masks2)]
+    B, C = args[0][5], args[0][6]
+    if any(x[5] != B or x[6] != C for x in args):
+        raise ValueError("every scale needs the same batch and channel count")
+    dev = args[0][1].device
+    Hs = _host_array(ctypes.c_int, [x[7] for x in args])
+    Ws = _host_array(ctypes.c_int, [x[8] for x in args])
+    npart = int(getattr(_lib.load(), f"usf_{kind.prefix}_loss_pyramid_partials")(n, Hs, Ws, B))
+    partials = torch.empty(npart, device=dev, dtype=torch.float32)
+    out = torch.empty((n, 2 * kind.nout), device=dev, dtype=torch.float32)
+    bases = None
+    if need_grad:
+        bases = [torch.empty((B, 2 * kind.planes, x[7], x[8]), device=dev, dtype=torch.float32) for x in args]
+    ptrs = lambda i: _host_array(ctypes.c_void_p, [x[i].data_ptr() for x in args])  # noqa: E731
+    nbytes = sum(4 * B * x[7] * x[8] * (2 * C + 4 + 2 + (2 * kind.planes if need_grad else 0)) for x in args)
+    key = (B, C) + tuple(v for x in args for v in (x[7], x[8])) + (pad,)
+    _loss_call(kind, "pyramid_fwd_f32", "pyr_grad" if need_grad else "pyr", key, dev, nbytes,
+               (n, ptrs(1), ptrs(2), ptrs(3), ptrs(4), ptrs(0), _host_array(ctypes.c_longlong, [x[9] for x in args]),
+                Hs, Ws, partials.data_ptr(), npart, out.data_ptr(),
+                _host_array(ctypes.c_void_p, [t.data_ptr() for t in bases]) if need_grad else None, B, C) + tail)
+    return out, bases
+
+
+def _loss_pyramid_backward(kind, bases, coef, grad_losses):
+    n, K = len(bases), 2 * kind.planes
+    for t in bases:
+        _require_device_f32("basis", t)
+        if t.dim() != 4 or t.shape[1] != K:
+            raise ValueError(f"gradient basis must be [B,{K},H,W], got {tuple(t.shape)}")
+    B = bases[0].shape[0]
+    dev = bases[0].device
+    gl = grad_losses.reshape(-1).to(torch.float32).contiguous()
+    if gl.numel() != 2 * n or coef.numel() != 2 * kind.nout * n:
+        raise ValueError(f"grad_losses / coef sizes {gl.numel()} / {coef.numel()} for {n} scales")
+    bases = [t.contiguous() for t in bases]
+    coef = coef.contiguous()
+    gflows = [torch.empty((B, 4) + tuple(t.shape[2:]), device=dev, dtype=torch.float32) for t in bases]
+    ptrs = lambda ts: _host_array(ctypes.c_void_p, [t.data_ptr() for t in ts])  # noqa: E731
+    key = (B, 2) + tuple(v for t in bases for v in t.shape[2:])
+    nbytes = sum(4 * B * t.shape[2] * t.shape[3] * (K + 4) for t in bases)
+    _loss_call(kind, "pyramid_bwd_f32", "pyr_bwd", key, dev, nbytes,
+               (n, ptrs(bases), coef.data_ptr(), gl.data_ptr(), ptrs(gflows),
+                _host_array(ctypes.c_int, [t.shape[2] for t in bases]),
+                _host_array(ctypes.c_int, [t.shape[3] for t in bases]), B))
+    return gflows
+
+
+def _loss_backward(kind, basis, coef, grad_loss):
+    _require_device_f32("basis", basis)
+    B, K, H, W = _nchw("basis", basis)
+    P = kind.planes
+    if K not in (P, 2 * P):
+        raise ValueError(f"gradient basis must be [B,{P},H,W] or [B,{2 * P},H,W], got {tuple(basis.shape)}")
+    ndir = K // P
+    basis = basis.contiguous()
+    coef = coef.contiguous()
+    gl = grad_loss.reshape(-1).to(torch.float32).contiguous()
+    if gl.numel() != ndir or coef.numel() != kind.nout * ndir:
+        raise ValueError(f"grad_loss / coef have {gl.numel()} / {coef.numel()} elements for {ndir} direction(s)")
+    gflow = torch.empty((B, 2 * ndir, H, W), device=basis.device, dtype=torch.float32)
+    _loss_call(kind, "bwd_f32", "bwd", (B, ndir, H, W), basis.device, 4 * B * H * W * (P + 2) * ndir,
+               (basis.data_ptr(), coef.data_ptr(), gl.data_ptr(), gflow.data_ptr(), B, H, W, ndir))
+    return gflow
+
+
+def photo_loss_forward(src, tgt, mask, flow, pad: str = "border", w_l1: float = 0.15, w_ssim: float = 0.85,
+                       need_grad: bool = False):
+    """Fused warp + occlusion-aware L1/SSIM photometric loss of one scale and
+    direction (flow_loss.py:127-148, loss_blocks.py:53-72) -> (out, basis):
+    ``out`` = tensor [3] on the device {loss, c_l1, c_ssim}; with ``need_grad``
+    ``basis`` = [B,4,H,W], the per-pixel flow-gradient basis computed in the
+    same pass (dL/dflow = c_l1 * basis[:, :2] + c_ssim * basis[:, 2:]), else None."""
+    return _loss_forward(_PHOTO, 1, flow, src, tgt, mask, None, pad, (w_l1, w_ssim), need_grad)
+
+
+def photo_loss_pair_forward(flow, im1, im2, mask1, mask2, pad: str = "border", w_l1: float = 0.15,
+                            w_ssim: float = 0.85, need_grad: bool = False):
     """Both directions of a with_bk scale in one launch (flow_loss.py:130-131):
     direction 0 = loss(im1, warp(im2, flow[:, :2]), mask1), direction 1 =
-    loss(im2, warp(im1, flow[:, 2:]), mask2) -> (out [4] = {loss, c_t} per
-    direction, basis [B,4,H,W] (= [B,2,2,H,W]) or None)."""
-    if pad not in PAD_MODES:
-        raise NotImplementedError(f"flow_warp padding mode {pad!r} (supported: border, zeros)")
-    fv, a, b_, m1, m2, B, C, H, W, fbs = _census_pair_args(flow, im1, im2, mask1, mask2)
-    lib = _lib.load()
-    partials = torch.empty(2 * lib.usf_census_loss_partials(B, H, W), device=a.device, dtype=torch.float32)
-    out = torch.empty(4, device=a.device, dtype=torch.float32)
-    basis = torch.empty((B, 4, H, W), device=a.device, dtype=torch.float32) if need_grad else None
-    # algorithmic bytes (each input read once): im1 and im2 (2C), the 4-channel
-    # flow, both masks; with the gradient the 4 basis planes written once
-    nbytes = 4 * B * H * W * (2 * C + 4 + 2 + (4 if need_grad else 0))
-    op = "census_pair_grad" if need_grad else "census_pair"
-    _args = (a.data_ptr(), b_.data_ptr(), m1.data_ptr(), m2.data_ptr(), fv.data_ptr(), fbs, partials.data_ptr(),
-             out.data_ptr(), basis.data_ptr() if need_grad else None, B, C, H, W, PAD_MODES[pad], float(w_ternary),
-             _lib.stream_handle(a.device),)
-    with torch.cuda.device(a.device), _kt.timed(op, (B, C, H, W, pad), a.device, nbytes):
-        rc = lib.usf_census_loss_pair_fwd_f32(*_args)
-    _lib.check(rc, "usf_census_loss_pair_fwd_f32")
-    return out, basis
+    loss(im2, warp(im1, flow[:, 2:]), mask2) -> (out [6] = {loss, c_l1, c_ssim}
+    per direction, basis [B,8,H,W] (= [B,2,4,H,W]) or None)."""
+    return _loss_forward(_PHOTO, 2, flow, im1, im2, mask1, mask2, pad, (w_l1, w_ssim), need_grad)
+
+
+def photo_loss_pyramid_forward(flows, im1s, im2s, masks1, masks2, pad: str = "border", w_l1: float = 0.15,
+                               w_ssim: float = 0.85, need_grad: bool = False):
+    """:func:`photo_loss_pair_forward` for up to 4 loss scales in one launch
+    (usf_photo_loss_pyramid_fwd_f32; the largest scale first) -> (out
+    [nscale, 6] = {loss, c_l1, c_ssim} per direction per scale, bases: a list
+    of [B,8,H_k,W_k] or None)."""
+    return _loss_pyramid_forward(_PHOTO, flows, im1s, im2s, masks1, masks2, pad, (w_l1, w_ssim), need_grad)
+
+
+def photo_loss_pyramid_backward(bases, coef, grad_losses):
+    """d(loss)/d(flow_k) * grad for every scale of :func:`photo_loss_pyramid_forward`
+    in one launch: bases [B,8,H_k,W_k], coef = its out [nscale, 6], grad_losses
+    [nscale, 2] -> list of [B,4,H_k,W_k] (deterministic)."""
+    return _loss_pyramid_backward(_PHOTO, bases, coef, grad_losses)
+
+
+def photo_loss_backward(basis, coef, grad_loss):
+    """d(photo loss)/d(flow) * grad_loss from the forward's gradient basis
+    ([B,4,H,W] one direction, [B,8,H,W] a pair) and coefficients ->
+    [B,2,H,W] / [B,4,H,W] (deterministic)."""
+    return _loss_backward(_PHOTO, basis, coef, grad_loss)
+
+
+def census_loss_forward(src, tgt, mask, flow, pad: str = "border", w_ternary: float = 1.0,
+                        need_grad: bool = False):
+    """:func:`photo_loss_forward` of the ternary (census) term (loss_blocks.py:12-50)
+    -> (out [2] = {loss, c_t}, basis [B,2,H,W] or None; dL/dflow = c_t * basis)."""
+    return _loss_forward(_CENSUS, 1, flow, src, tgt, mask, None, pad, (w_ternary,), need_grad)
+
+
+def census_loss_pair_forward(flow, im1, im2, mask1, mask2, pad: str = "border", w_ternary: float = 1.0,
+                             need_grad: bool = False):
+    """:func:`photo_loss_pair_forward` of the census term -> (out [4] = {loss, c_t}
+    per direction, basis [B,4,H,W] (= [B,2,2,H,W]) or None)."""
+    return _loss_forward(_CENSUS, 2, flow, im1, im2, mask1, mask2, pad, (w_ternary,), need_grad)
 
 
 def census_loss_pyramid_forward(flows, im1s, im2s, masks1, masks2, pad: str = "border", w_ternary: float = 1.0,
                                 need_grad: bool = False):
-    """:func:`census_loss_pair_forward` for up to 4 loss scales in one launch
-    (usf_census_loss_pyramid_fwd_f32; the largest scale first) -> (out
-    [nscale, 4] = {loss, c_t} per direction per scale, bases: a list of
-    [B,4,H_k,W_k] or None)."""
-    import ctypes
-
-    if pad not in PAD_MODES:
-        raise NotImplementedError(f"flow_warp padding mode {pad!r} (supported: border, zeros)")
-    n = len(flows)
-    if not 1 <= n <= 4 or not (len(im1s) == len(im2s) == len(masks1) == len(masks2) == n):
-        raise ValueError(f"1..4 scales with one flow, two images and two masks each (got {n})")
-    args = [_census_pair_args(*x) for x in zip(flows, im1s, im2s, masks1, masks2)]
-    B, C = args[0][5], args[0][6]
-    if any(x[5] != B for x in args):
-        raise ValueError("every scale needs the same batch size")
-    dev = args[0][1].device
-    Hs = _host_array(ctypes.c_int, [x[7] for x in args])
-    Ws = _host_array(ctypes.c_int, [x[8] for x in args])
-    lib = _lib.load()
-    npart = int(lib.usf_census_loss_pyramid_partials(n, Hs, Ws, B))
-    partials = torch.empty(npart, device=dev, dtype=torch.float32)
-    out = torch.empty((n, 4), device=dev, dtype=torch.float32)
-    bases = [torch.empty((B, 4, x[7], x[8]), device=dev, dtype=torch.float32) for x in args] if need_grad else None
-    ptrs = lambda i: _host_array(ctypes.c_void_p, [x[i].data_ptr() for x in args])  # noqa: E731
-    nbytes = sum(4 * B * x[7] * x[8] * (2 * C + 4 + 2 + (4 if need_grad else 0)) for x in args)
-    op = "census_pyr_grad" if need_grad else "census_pyr"
-    key = (B, C) + tuple(v for x in args for v in (x[7], x[8])) + (pad,)
-    _args = (n, ptrs(1), ptrs(2), ptrs(3), ptrs(4), ptrs(0), _host_array(ctypes.c_longlong, [x[9] for x in args]),
-             Hs, Ws, partials.data_ptr(), npart, out.data_ptr(),
-             _host_array(ctypes.c_void_p, [t.data_ptr() for t in bases]) if need_grad else None, B, C,
-             PAD_MODES[pad], float(w_ternary), _lib.stream_handle(dev),)
-    with torch.cuda.device(dev), _kt.timed(op, key, dev, nbytes):
-        rc = lib.usf_census_loss_pyramid_fwd_f32(*_args)
-    _lib.check(rc, "usf_census_loss_pyramid_fwd_f32")
-    return out, bases
+    """:func:`census_loss_pair_forward` for up to 4 loss scales in one launch -> (out
+    [nscale, 4] = {loss, c_t} per direction per scale, bases: a list of [B,4,H_k,W_k] or None)."""
+    return _loss_pyramid_forward(_CENSUS, flows, im1s, im2s, masks1, masks2, pad, (w_ternary,), need_grad)
 
 
 def census_loss_pyramid_backward(bases, coef, grad_losses):
-    """d(loss)/d(flow_k) * grad for every scale of :func:`census_loss_pyramid_forward`
-    in one launch: bases [B,4,H_k,W_k], coef = its out [nscale, 4], grad_losses
-    [nscale, 2] -> list of [B,4,H_k,W_k] (deterministic)."""
-    import ctypes
-
-    n = len(bases)
-    for t in bases:
-        _require_device_f32("basis", t)
-        if t.dim() != 4 or t.shape[1] != 4:
-            raise ValueError(f"gradient basis must be [B,4,H,W], got {tuple(t.shape)}")
-    B = bases[0].shape[0]
-    dev = bases[0].device
-    gl = grad_losses.reshape(-1).to(torch.float32).contiguous()
-    if gl.numel() != 2 * n or coef.numel() != 4 * n:
-        raise ValueError(f"grad_losses / coef sizes {gl.numel()} / {coef.numel()} for {n} scales")
-    bases = [t.contiguous() for t in bases]
-    coef = coef.contiguous()
-    gflows = [torch.empty_like(t) for t in bases]
-    Hs = _host_array(ctypes.c_int, [t.shape[2] for t in bases])
-    Ws = _host_array(ctypes.c_int, [t.shape[3] for t in bases])
-    lib = _lib.load()
-    key = (B, 2) + tuple(v for t in bases for v in t.shape[2:])
-    nbytes = sum(4 * B * t.shape[2] * t.shape[3] * 8 for t in bases)
-    _args = (n, _host_array(ctypes.c_void_p, [t.data_ptr() for t in bases]), coef.data_ptr(), gl.data_ptr(),
-             _host_array(ctypes.c_void_p, [t.data_ptr() for t in gflows]), Hs, Ws, B, _lib.stream_handle(dev),)
-    with torch.cuda.device(dev), _kt.timed("census_pyr_bwd", key, dev, nbytes):
-        rc = lib.usf_census_loss_pyramid_bwd_f32(*_args)
-    _lib.check(rc, "usf_census_loss_pyramid_bwd_f32")
-    return gflows
+    """:func:`photo_loss_pyramid_backward` of the census term: bases [B,4,H_k,W_k], coef
+    [nscale, 4], grad_losses [nscale, 2] -> list of [B,4,H_k,W_k] (deterministic)."""
+    return _loss_pyramid_backward(_CENSUS, bases, coef, grad_losses)
 
 
 def census_loss_backward(basis, coef, grad_loss):
-    """d(census loss)/d(flow) * grad_loss from the forward's gradient basis
-    ([B,2,H,W] one direction, [B,4,H,W] a pair) and coefficients -> the same
-    shape (deterministic)."""
-    _require_device_f32("basis", basis)
-    B, K, H, W = _nchw("basis", basis)
-    if K not in (2, 4):
-        raise ValueError(f"gradient basis must be [B,2,H,W] or [B,4,H,W], got {tuple(basis.shape)}")
-    ndir = K // 2
-    basis = basis.contiguous()
-    coef = coef.contiguous()
-    gl = grad_loss.reshape(-1).to(torch.float32).contiguous()
-    if gl.numel() != ndir or coef.numel() != 2 * ndir:
-        raise ValueError(f"grad_loss / coef have {gl.numel()} / {coef.numel()} elements for {ndir} direction(s)")
-    gflow = torch.empty_like(basis)
-    lib = _lib.load()
-    _args = (basis.data_ptr(), coef.data_ptr(), gl.data_ptr(), gflow.data_ptr(), B, H, W, ndir,
-             _lib.stream_handle(basis.device),)
-    with torch.cuda.device(basis.device), _kt.timed("census_bwd", (B, ndir, H, W), basis.device,
-                                                      4 * B * H * W * 4 * ndir):
-        rc = lib.usf_census_loss_bwd_f32(*_args)
-    _lib.check(rc, "usf_census_loss_bwd_f32")
-    return gflow
+    """:func:`photo_loss_backward` of the census term: basis [B,2,H,W] (one direction)
+    or [B,4,H,W] (a pair) and coefficients -> the same shape (deterministic)."""
+    return _loss_backward(_CENSUS, basis, coef, grad_loss)
 
 
 def ar_transform(img1, img2, flow, mask, theta, noise1=None, noise2=None):
