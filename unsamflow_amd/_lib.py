@@ -203,6 +203,24 @@ AR_SYMBOLS = {
     ),
 }
 
+# the mask-feature branch's per-segment max pool and spread
+# (include/unsamflow_hip_segpool.h), versioned the same way
+SEGPOOL_API_VERSION = 1
+SEGPOOL_MAX_K = 1024
+DEVERR_SEGPOOL_BAD_ID = 4
+SEGPOOL_SYMBOLS = {
+    "usf_segpool_api_version": ([], ctypes.c_int),
+    "usf_segpool_state_words": ([ctypes.c_int] * 3, ctypes.c_longlong),
+    "usf_segpool_fwd_f32": (
+        [_c_float_p] * 3 + [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+    "usf_segpool_bwd_f32": (
+        [_c_float_p] * 2 + [ctypes.c_void_p] + [_c_float_p] * 2 + [ctypes.c_int] * 5 + [ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+}
+
 _lock = threading.Lock()
 _lib = None
 _load_error: str | None = None
@@ -227,7 +245,7 @@ def load() -> ctypes.CDLL:
             )
             raise RuntimeError(_load_error)
         lib = ctypes.CDLL(str(_LIB_PATH), mode=ctypes.RTLD_LOCAL)
-        for name, (argtypes, restype) in {**_SIGNATURES, **CENSUS_SYMBOLS, **AR_SYMBOLS}.items():
+        for name, (argtypes, restype) in {**_SIGNATURES, **CENSUS_SYMBOLS, **AR_SYMBOLS, **SEGPOOL_SYMBOLS}.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = restype
@@ -240,6 +258,9 @@ def load() -> ctypes.CDLL:
         v = lib.usf_ar_api_version()
         if v != AR_API_VERSION:
             raise RuntimeError(f"libunsamflow_hip.so AR API version {v} != expected {AR_API_VERSION}")
+        v = lib.usf_segpool_api_version()
+        if v != SEGPOOL_API_VERSION:
+            raise RuntimeError(f"libunsamflow_hip.so segpool API version {v} != expected {SEGPOOL_API_VERSION}")
         _lib = lib
         return lib
 

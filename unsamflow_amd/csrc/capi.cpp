@@ -11,6 +11,7 @@
 #include "../../include/unsamflow_hip.h"
 #include "../../include/unsamflow_hip_ar.h"
 #include "../../include/unsamflow_hip_census.h"
+#include "../../include/unsamflow_hip_segpool.h"
 #include "usf_common.h"
 
 namespace usf {
@@ -78,7 +79,8 @@ static int finish(const char* fn, hipError_t e, hipStream_t s) {
   if (e == hipSuccess && sync_check_on(s)) {
     e = hipStreamSynchronize(s);
     if (e != hipSuccess) fprintf(stderr, "[usf] %s: fault after launch: %s\n", fn, hipGetErrorString(e));
-    const int flags = e == hipSuccess ? device_errors(s, true) : 0;
+    // a bad segment id is the caller's data, not a failed launch: left for usf_device_errors
+    const int flags = e == hipSuccess ? device_errors(s, true, ~USF_DEVERR_SEGPOOL_BAD_ID) : 0;
     if (flags > 0) {
       fprintf(stderr, "[usf] %s: device error flags 0x%x\n", fn, flags);
       set_error("%s: device error flags 0x%x", fn, flags);
@@ -833,6 +835,74 @@ int usf_ar_loss_bwd_f32(const float* pred, const float* target, long long target
   return finish(fn,
                 ar_loss_bwd_launch(pred, target, target_bstride, target_cstride, target_rstride, noc, noc_bstride,
                                    noc_rstride, coef, grad_loss, grad_pred, B, H, W, eps, q, (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+// ------------------------------------------------ unsamflow_hip_segpool.h --
+int usf_segpool_api_version(void) { return USF_SEGPOOL_API_VERSION; }
+
+static bool check_segpool(const char* fn, int B, int C, int H, int W, int K) {
+  if (!check_dims(fn, B, C, H, W)) return false;
+  if (B > 65535 || C > 65535) {
+    set_error("%s: B=%d C=%d (at most 65535 each)", fn, B, C);
+    return false;
+  }
+  if (K < 1 || K > USF_SEGPOOL_MAX_K) {
+    set_error("%s: K=%d outside [1, %d]", fn, K, USF_SEGPOOL_MAX_K);
+    return false;
+  }
+  return true;
+}
+
+long long usf_segpool_state_words(int B, int C, int K) {
+  return (B > 0 && C > 0 && K >= 1 && K <= USF_SEGPOOL_MAX_K) ? segpool_state_words(B, C, K) : 0;
+}
+
+int usf_segpool_fwd_f32(const float* proj, const float* seg, float* spread, void* state, int B, int C, int H, int W,
+                        int K, void* stream) {
+  clear_error();
+  const char* fn = "usf_segpool_fwd_f32";
+  if (!check_segpool(fn, B, C, H, W, K)) return USF_EINVAL;
+  if (!proj || !seg) {
+    set_error("%s: null input pointer", fn);
+    return USF_EINVAL;
+  }
+  if (!spread || !state) {
+    set_error("%s: null output pointer", fn);
+    return USF_EINVAL;
+  }
+  if ((uintptr_t)state % 4 != 0) {
+    set_error("%s: state not 4-byte aligned", fn);
+    return USF_EINVAL;
+  }
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn,
+                segpool_fwd_launch(proj, seg, spread, static_cast<unsigned*>(state), B, C, H, W, K,
+                                   (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+int usf_segpool_bwd_f32(const float* proj, const float* seg, const void* state, const float* grad_spread,
+                        float* grad_proj, int B, int C, int H, int W, int K, void* stream) {
+  clear_error();
+  const char* fn = "usf_segpool_bwd_f32";
+  if (!check_segpool(fn, B, C, H, W, K)) return USF_EINVAL;
+  if (!proj || !seg || !state || !grad_spread) {
+    set_error("%s: null input pointer", fn);
+    return USF_EINVAL;
+  }
+  if (!grad_proj) {
+    set_error("%s: null output pointer", fn);
+    return USF_EINVAL;
+  }
+  if ((uintptr_t)state % 4 != 0) {
+    set_error("%s: state not 4-byte aligned", fn);
+    return USF_EINVAL;
+  }
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn,
+                segpool_bwd_launch(proj, seg, static_cast<const unsigned*>(state), grad_spread, grad_proj, B, C, H, W,
+                                   K, (hipStream_t)stream),
                 (hipStream_t)stream);
 }
 

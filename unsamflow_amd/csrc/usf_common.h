@@ -9,8 +9,9 @@
 namespace usf {
 
 // Device-side error flags (warp.hip): read and optionally cleared after a
-// stream sync; -1 if the sync or the copy failed.
-int device_errors(hipStream_t s, bool clear);
+// stream sync; -1 if the sync or the copy failed. Only the flags in `mask` are
+// reported and cleared.
+int device_errors(hipStream_t s, bool clear, int mask = ~0);
 
 // Thread-local error slot behind usf_last_error_string().
 void set_error(const char* fmt, ...);
@@ -177,6 +178,14 @@ hipError_t ar_loss_fwd_launch(const float* pred, const float* target, long long 
 hipError_t ar_loss_bwd_launch(const float* pred, const float* target, long long tbs, long long tcs, long long trs,
                               const float* noc, long long nbs, long long nrs, const float* coef, const float* gloss,
                               float* gpred, int B, int H, int W, float eps, float q, hipStream_t s);
+
+// segpool.hip: the mask-feature branch's per-segment max pool and spread
+int segpool_device_errors(bool clear);  // this code object's flags (device_errors() adds them)
+long long segpool_state_words(int B, int C, int K);
+hipError_t segpool_fwd_launch(const float* proj, const float* seg, float* spread, unsigned* state, int B, int C,
+                              int H, int W, int K, hipStream_t s);
+hipError_t segpool_bwd_launch(const float* proj, const float* seg, const unsigned* state, const float* gs, float* gp,
+                              int B, int C, int H, int W, int K, hipStream_t s);
 
 hipError_t upsample_fwd_launch(const float* x, float* out, int B, int C, int H, int W, int k,
                                hipStream_t s);

@@ -27,6 +27,7 @@
 
 #include "interp_tap.h"
 #include "usf_common.h"
+#include "../../include/unsamflow_hip_segpool.h"
 #include "warp_tap.h"
 
 namespace usf {
@@ -1573,15 +1574,18 @@ __global__ __launch_bounds__(256) void occ_vis_pair_kernel(float* __restrict__ m
 
 }  // namespace
 
-int device_errors(hipStream_t s, bool clear) {
+int device_errors(hipStream_t s, bool clear, int mask) {
   int v = 0;
   if (hipStreamSynchronize(s) != hipSuccess) return -1;
   if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_dev_errors), sizeof(int)) != hipSuccess) return -1;
-  if (clear && v != 0) {
-    const int z = 0;
+  if (clear && (v & mask) != 0) {
+    const int z = v & ~mask;
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_dev_errors), &z, sizeof(int)) != hipSuccess) return -1;
   }
-  return v;
+  v &= mask;
+  // segpool.hip keeps its own flag word (one code object per source file)
+  const int sp = (mask & USF_DEVERR_SEGPOOL_BAD_ID) ? segpool_device_errors(clear) : 0;
+  return sp < 0 ? -1 : (v | sp);
 }
 
 hipError_t warp_fwd_launch(const float* x, const float* flow, long long fbs, float* out, int B,

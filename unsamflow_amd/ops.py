@@ -738,6 +738,74 @@ def ar_loss_backward(pred, target, noc, coef, grad_loss, eps: float = 0.0, q: fl
     return gpred
 
 
+def _segpool_args(proj, seg, num_segments):
+    _require_device_f32("proj", proj)
+    _require_device_f32("seg", seg)
+    B, C, H, W = _nchw("proj", proj)
+    if tuple(seg.shape) != (B, 1, H, W):
+        raise ValueError(f"seg must be [B,1,h,w] = {(B, 1, H, W)}, got {tuple(seg.shape)}")
+    if seg.device != proj.device:
+        raise ValueError("proj and seg are on different devices")
+    K = int(num_segments)
+    if not 1 <= K <= _lib.SEGPOOL_MAX_K:
+        raise ValueError(f"num_segments={K} outside [1, {_lib.SEGPOOL_MAX_K}] (USF_SEGPOOL_MAX_K)")
+    return proj.contiguous(), seg.contiguous(), B, C, H, W, K
+
+
+def segpool_forward(proj, seg, num_segments: int):
+    """Per-segment max pool and spread (pwclite.py:317-357): ``spread[b,c,p] =
+    pooled[b,c,seg[b,p]]`` with ``pooled = amax(one_hot(seg) * proj[..., None],
+    dim=(2, 3))``. proj [B,C,h,w]; seg [B,1,h,w] fp32 integer ids in
+    [0, num_segments) -> (spread [B,C,h,w], state), the int32 tables (maxima,
+    pixel counts) :func:`segpool_backward` reads."""
+    p, s, B, C, H, W, K = _segpool_args(proj, seg, num_segments)
+    dev = p.device
+    lib = _lib.load()
+    state = torch.empty(lib.usf_segpool_state_words(B, C, K), device=dev, dtype=torch.int32)
+    spread = torch.empty_like(p)
+    _args = (p.data_ptr(), s.data_ptr(), spread.data_ptr(), state.data_ptr(), B, C, H, W, K,
+             _lib.stream_handle(dev),)
+    # algorithmic bytes: proj and seg read once, spread written
+    with torch.cuda.device(dev), _kt.timed("segpool_fwd", (B, C, H, W, K), dev, B * H * W * (8 * C + 4)):
+        rc = lib.usf_segpool_fwd_f32(*_args)
+    _lib.check(rc, "usf_segpool_fwd_f32")
+    return spread, state
+
+
+def segpool_backward(proj, seg, state, grad_spread, num_segments: int):
+    """d(spread)/d(proj) applied to ``grad_spread`` -> [B,C,h,w]: a segment's
+    summed gradient shared evenly among the positions equal to its pooled value
+    (the one-hot product's zeros outside the segment included)."""
+    p, s, B, C, H, W, K = _segpool_args(proj, seg, num_segments)
+    dev = p.device
+    _require_device_f32("grad_spread", grad_spread)
+    if tuple(grad_spread.shape) != (B, C, H, W) or grad_spread.device != dev:
+        raise ValueError(f"grad_spread {tuple(grad_spread.shape)} does not match proj {(B, C, H, W)}")
+    lib = _lib.load()
+    if (state.dtype != torch.int32 or state.device != dev or not state.is_contiguous()
+            or state.numel() != lib.usf_segpool_state_words(B, C, K)):
+        raise ValueError("state is not the forward's table buffer for this shape")
+    g = grad_spread.contiguous()
+    gproj = torch.empty_like(p)
+    _args = (p.data_ptr(), s.data_ptr(), state.data_ptr(), g.data_ptr(), gproj.data_ptr(), B, C, H, W, K,
+             _lib.stream_handle(dev),)
+    # algorithmic bytes: proj, grad_spread and seg read once, grad_proj written
+    with torch.cuda.device(dev), _kt.timed("segpool_bwd", (B, C, H, W, K), dev, B * H * W * (12 * C + 8)):
+        rc = lib.usf_segpool_bwd_f32(*_args)
+    _lib.check(rc, "usf_segpool_bwd_f32")
+    return gproj
+
+
+def device_errors(device, clear: bool = True) -> int:
+    """The USF_DEVERR_* flags kernels raised on ``device``'s current stream since
+    the last clear (usf_device_errors; synchronises the stream)."""
+    with torch.cuda.device(device):
+        v = _lib.load().usf_device_errors(_lib.stream_handle(torch.device(device)), 1 if clear else 0)
+    if v < 0:
+        _lib.check(v, "usf_device_errors")
+    return v
+
+
 def _plane_slice_stride(name: str, t: torch.Tensor, shape) -> int:
     """Batch stride of a [B,K,H,W] channel slice whose per-sample planes are dense."""
     B, K, H, W = shape

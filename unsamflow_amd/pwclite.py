@@ -159,6 +159,13 @@ def _default_corr():
 
 # the decoder's x2 flow upsampling and warp of x2 as one launch (upsample.upsample_warp)
 FUSED_UP_WARP = True
+# the mask-feature branch's per-segment max pool and spread as HIP kernels
+# (segpool.segment_max_spread) instead of the one-hot composition (the same numbers)
+FUSED_SEG_POOL = True
+# with_bk as one pass at batch 2B: frame 2's mask features are frame 1's with the
+# batch halves swapped, so the branch (1x1 conv, pool, aggregation) runs once per
+# level; only the order of its weight-gradient sums over the batch changes
+SHARED_MASK_FEATURE = True
 
 
 def _default_warp():
@@ -212,12 +219,34 @@ class PWCLite(nn.Module):
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
 
     # -- mask-feature branch (pwclite.py:317-357) ------------------------------
-    def _mask_feature(self, x, full_seg, level):
+    def _own_ops_on_device(self, x) -> bool:
+        """The library's own ops on a ROCm device (the condition of fused_corr_cat)."""
+        return self.fused_corr_cat and x.is_cuda
+
+    def _segment_count(self, x, *full_segs):
+        """K of the fused pooling, once per forward: ``cfg.num_segments`` when
+        present (no host sync), else the full-resolution maps' largest id + 1
+        (one sync per step instead of F.one_hot's one per call)."""
+        if not (self.cfg.add_mask_corr and FUSED_SEG_POOL and self._own_ops_on_device(x)):
+            return None
+        if "num_segments" in self.cfg:
+            return int(self.cfg.num_segments)
+        top = full_segs[0].max()
+        for s in full_segs[1:]:
+            top = torch.maximum(top, s.max())
+        return int(top) + 1
+
+    def _mask_feature(self, x, full_seg, level, num_segments=None):
         proj = self.conv_1x1_mask[level](x)
-        seg = F.interpolate(full_seg, x.shape[-2:], mode="nearest").long()
-        onehot = F.one_hot(seg)  # [B,1,h,w,K]
-        pooled = torch.amax(onehot * proj[..., None], dim=(2, 3))  # [B,32,K]: per-segment max
-        spread = (onehot * pooled[:, :, None, None, :]).sum(dim=-1)  # back to pixels
+        seg = F.interpolate(full_seg, x.shape[-2:], mode="nearest")
+        if FUSED_SEG_POOL and self._own_ops_on_device(x):
+            from .segpool import segment_max_spread
+
+            spread = segment_max_spread(proj, seg, num_segments)
+        else:
+            onehot = F.one_hot(seg.long())  # [B,1,h,w,K]
+            pooled = torch.amax(onehot * proj[..., None], dim=(2, 3))  # [B,32,K]: per-segment max
+            spread = (onehot * pooled[:, :, None, None, :]).sum(dim=-1)  # back to pixels
         if self.cfg.aggregation_type == "residual":
             return proj + self.mask_aggregation(spread)
         if self.cfg.aggregation_type == "concat":
@@ -239,7 +268,10 @@ class PWCLite(nn.Module):
 
         return FUSED_UP_WARP and self.fused_corr_cat and flow.is_cuda and self.warp is flow_warp
 
-    def decoder(self, x1_pyramid, x2_pyramid, full_seg1=None, full_seg2=None):
+    def decoder(self, x1_pyramid, x2_pyramid, full_seg1=None, full_seg2=None, num_segments=None,
+                swapped_half=None):
+        """``swapped_half`` = B: the second pyramid and segment maps are the first
+        ones with the batch halves [:B], [B:] swapped (_forward_batched)."""
         flows, deferred = [], []
         B, _, h0, w0 = x1_pyramid[0].size()
         flow = torch.zeros(B, 2, h0, w0, dtype=x1_pyramid[0].dtype, device=x1_pyramid[0].device).float()
@@ -256,8 +288,11 @@ class PWCLite(nn.Module):
                 x2_warp = x2
             pairs = [(x1, x2_warp)]
             if self.cfg.add_mask_corr:
-                m1 = self._mask_feature(x1, full_seg1, level)
-                m2 = self._mask_feature(x2, full_seg2, level)
+                m1 = self._mask_feature(x1, full_seg1, level, num_segments)
+                if swapped_half is not None and SHARED_MASK_FEATURE and self._own_ops_on_device(x1):
+                    m2 = torch.cat((m1[swapped_half:], m1[:swapped_half]), dim=0)
+                else:
+                    m2 = self._mask_feature(x2, full_seg2, level, num_segments)
                 pairs.append((m1, self.warp(m2, flow)))
             extras = [self.conv_1x1[level](x1), flow]
             if self.fused_corr_cat and x1.is_cuda:
@@ -310,9 +345,10 @@ class PWCLite(nn.Module):
             return self._forward_batched(img1, img2, full_seg1, full_seg2, adj1, adj2)
         feat1 = self.feature_pyramid_extractor(img1, adj1)
         feat2 = self.feature_pyramid_extractor(img2, adj2)
-        res = {"flows_12": self.decoder(feat1, feat2, full_seg1, full_seg2)}
+        nseg = self._segment_count(img1, full_seg1, full_seg2) if full_seg1 is not None else None
+        res = {"flows_12": self.decoder(feat1, feat2, full_seg1, full_seg2, nseg)}
         if with_bk:
-            res["flows_21"] = self.decoder(feat2, feat1, full_seg2, full_seg1)
+            res["flows_21"] = self.decoder(feat2, feat1, full_seg2, full_seg1, nseg)
         return res
 
     def _forward_batched(self, img1, img2, full_seg1, full_seg2, adj1, adj2):
@@ -329,9 +365,10 @@ class PWCLite(nn.Module):
         feats = self.feature_pyramid_extractor(torch.cat((img1, img2), dim=0), adj)
         used = feats[: self.output_level + 1]
         swapped = [torch.cat((f[B:], f[:B]), dim=0) for f in used]
-        seg_a = seg_b = None
+        seg_a = seg_b = nseg = None
         if full_seg1 is not None:
             seg_a = torch.cat((full_seg1, full_seg2), dim=0)
             seg_b = torch.cat((full_seg2, full_seg1), dim=0)
-        flows = self.decoder(used, swapped, seg_a, seg_b)
+            nseg = self._segment_count(img1, seg_a)
+        flows = self.decoder(used, swapped, seg_a, seg_b, nseg, swapped_half=B)
         return {"flows_12": [f[:B] for f in flows], "flows_21": [f[B:] for f in flows]}
