@@ -221,6 +221,34 @@ SEGPOOL_SYMBOLS = {
     ),
 }
 
+# the homography smoothness loss (include/unsamflow_hip_hg.h), versioned the same way
+HG_API_VERSION = 1
+HG_MAX_K = 1024
+HG_SLOTS = 6
+HG_RECORD_WORDS = 16
+HG_DEFAULT_HYP = 256
+HG_STATUS = ("accepted", "too few reliable", "low reliable share", "low inlier share", "degenerate", "empty slot")
+DEVERR_HG_BAD_ID = 8
+_hg_flow = [_c_float_p, ctypes.c_longlong, _c_float_p]
+HG_SYMBOLS = {
+    "usf_hg_api_version": ([], ctypes.c_int),
+    "usf_hg_workspace_bytes": ([ctypes.c_int] * 5, ctypes.c_longlong),
+    "usf_hg_fit_f32": (
+        _hg_flow + [_c_float_p, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_void_p,
+                    ctypes.c_void_p, ctypes.c_longlong] + [ctypes.c_int] * 3 + [ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+    "usf_hg_loss_partials": ([ctypes.c_int] * 3, ctypes.c_int),
+    "usf_hg_loss_fwd_f32": (
+        _hg_flow + [ctypes.c_void_p, ctypes.c_void_p, _c_float_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+    "usf_hg_loss_bwd_f32": (
+        _hg_flow + [ctypes.c_void_p, _c_float_p, _c_float_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+}
+
 _lock = threading.Lock()
 _lib = None
 _load_error: str | None = None
@@ -245,7 +273,8 @@ def load() -> ctypes.CDLL:
             )
             raise RuntimeError(_load_error)
         lib = ctypes.CDLL(str(_LIB_PATH), mode=ctypes.RTLD_LOCAL)
-        for name, (argtypes, restype) in {**_SIGNATURES, **CENSUS_SYMBOLS, **AR_SYMBOLS, **SEGPOOL_SYMBOLS}.items():
+        for name, (argtypes, restype) in {**_SIGNATURES, **CENSUS_SYMBOLS, **AR_SYMBOLS, **SEGPOOL_SYMBOLS,
+                                          **HG_SYMBOLS}.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = restype
@@ -261,6 +290,9 @@ def load() -> ctypes.CDLL:
         v = lib.usf_segpool_api_version()
         if v != SEGPOOL_API_VERSION:
             raise RuntimeError(f"libunsamflow_hip.so segpool API version {v} != expected {SEGPOOL_API_VERSION}")
+        v = lib.usf_hg_api_version()
+        if v != HG_API_VERSION:
+            raise RuntimeError(f"libunsamflow_hip.so hg API version {v} != expected {HG_API_VERSION}")
         _lib = lib
         return lib
 

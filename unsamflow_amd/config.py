@@ -16,6 +16,13 @@ reference's JSON configs:
   ``run_ot``, ``ot_size``) and the train keys the augmentation branch reads
   (``w_ar``, ``ar_eps``, ``ar_q``, ``mask_st``, ``st_cfg``): the step of
   epochs 50-200 (unsamflow_amd.ar, harness.TrainStep)
+* ``kitti_stage2_hg()`` / ``sintel_stage2_hg()`` — the stage-1 AR config with
+  the ``train.stage2`` overrides of configs/kitti_aug+hg.json /
+  configs/sintel_aug+hg.json applied (from epoch 150): the homography
+  smoothness loss (``smooth_type "homography"``, ``w_sm 0.1``, KITTI
+  ``ransac_threshold 0.5``; Sintel leaves it to unFlowLoss's default of 3) and
+  ``w_ar 0.1``. ``key_obj_aug`` stays ``False``: fake-object insertion is not
+  built (unsamflow_amd.homography, flow_loss.unFlowLoss)
 
 ``load_json`` reads a reference-format JSON file with the one-level
 ``base_configs`` inheritance + recursive merge of utils/config_parser.py:11-33.
@@ -166,4 +173,22 @@ def sintel_stage1_ar() -> AttrDict:
     cfg = sintel_stage1()
     cfg.train.update(AttrDict.wrap(dict(copy.deepcopy(_AR_TRAIN), ot_size=[320, 704],
                                         st_cfg=copy.deepcopy(_ST_CFG_SINTEL))))
+    return cfg
+
+
+# train.stage2 of configs/kitti_aug+hg.json and configs/sintel_aug+hg.json (key_obj_aug aside)
+_STAGE2_HG_LOSS = {"smooth_type": "homography", "w_sm": 0.1}
+
+
+def kitti_stage2_hg() -> AttrDict:
+    cfg = kitti_stage1_ar()
+    cfg.loss.update(dict(_STAGE2_HG_LOSS, ransac_threshold=0.5))
+    cfg.train.w_ar = 0.1
+    return cfg
+
+
+def sintel_stage2_hg() -> AttrDict:
+    cfg = sintel_stage1_ar()
+    cfg.loss.update(_STAGE2_HG_LOSS)
+    cfg.train.w_ar = 0.1
     return cfg

@@ -11,6 +11,7 @@
 #include "../../include/unsamflow_hip.h"
 #include "../../include/unsamflow_hip_ar.h"
 #include "../../include/unsamflow_hip_census.h"
+#include "../../include/unsamflow_hip_hg.h"
 #include "../../include/unsamflow_hip_segpool.h"
 #include "usf_common.h"
 
@@ -80,7 +81,8 @@ static int finish(const char* fn, hipError_t e, hipStream_t s) {
     e = hipStreamSynchronize(s);
     if (e != hipSuccess) fprintf(stderr, "[usf] %s: fault after launch: %s\n", fn, hipGetErrorString(e));
     // a bad segment id is the caller's data, not a failed launch: left for usf_device_errors
-    const int flags = e == hipSuccess ? device_errors(s, true, ~USF_DEVERR_SEGPOOL_BAD_ID) : 0;
+    const int flags =
+        e == hipSuccess ? device_errors(s, true, ~(USF_DEVERR_SEGPOOL_BAD_ID | USF_DEVERR_HG_BAD_ID)) : 0;
     if (flags > 0) {
       fprintf(stderr, "[usf] %s: device error flags 0x%x\n", fn, flags);
       set_error("%s: device error flags 0x%x", fn, flags);
@@ -903,6 +905,129 @@ int usf_segpool_bwd_f32(const float* proj, const float* seg, const void* state, 
   return finish(fn,
                 segpool_bwd_launch(proj, seg, static_cast<const unsigned*>(state), grad_spread, grad_proj, B, C, H, W,
                                    K, (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+// ----------------------------------------------------- unsamflow_hip_hg.h --
+int usf_hg_api_version(void) { return USF_HG_API_VERSION; }
+
+// shape and flow stride of every hg entry
+static bool check_hg(const char* fn, int B, int H, int W, long long fbs) {
+  if (!check_dims(fn, B, 2, H, W)) return false;
+  if (B > 65535) {
+    set_error("%s: B=%d (at most 65535)", fn, B);
+    return false;
+  }
+  if (fbs < 2ll * H * W) {
+    set_error("%s: flow_bstride=%lld below 2*H*W=%lld", fn, fbs, 2ll * H * W);
+    return false;
+  }
+  return true;
+}
+
+static bool check_hg_fit(const char* fn, int K, float thr, int n_hyp) {
+  if (K < 1 || K > USF_HG_MAX_K) {
+    set_error("%s: K=%d outside [1, %d]", fn, K, USF_HG_MAX_K);
+    return false;
+  }
+  if (n_hyp < 1 || n_hyp > USF_HG_MAX_HYP) {
+    set_error("%s: n_hyp=%d outside [1, %d]", fn, n_hyp, USF_HG_MAX_HYP);
+    return false;
+  }
+  if (!(thr > 0.f) || !(thr < 1e18f)) {
+    set_error("%s: thr=%g (need a finite thr > 0)", fn, (double)thr);
+    return false;
+  }
+  return true;
+}
+
+long long usf_hg_workspace_bytes(int B, int H, int W, int K, int n_hyp) {
+  if (B <= 0 || B > 65535 || H <= 0 || W <= 0 || (long long)H * W > 0x1FFFFFFFLL || K < 1 || K > USF_HG_MAX_K ||
+      n_hyp < 1 || n_hyp > USF_HG_MAX_HYP)
+    return 0;
+  return hg_workspace_bytes(B, H, W, K, n_hyp);
+}
+
+int usf_hg_fit_f32(const float* flow, long long flow_bstride, const float* seg, const float* occ, int K, float thr,
+                   int n_hyp, unsigned long long seed, void* records, void* workspace, long long workspace_bytes,
+                   int B, int H, int W, void* stream) {
+  clear_error();
+  const char* fn = "usf_hg_fit_f32";
+  if (!check_hg(fn, B, H, W, flow_bstride) || !check_hg_fit(fn, K, thr, n_hyp)) return USF_EINVAL;
+  if (!flow || !seg || !occ) {
+    set_error("%s: null input pointer", fn);
+    return USF_EINVAL;
+  }
+  if (!records || !workspace) {
+    set_error("%s: null output pointer", fn);
+    return USF_EINVAL;
+  }
+  if ((uintptr_t)records % 4 != 0 || (uintptr_t)workspace % 8 != 0) {
+    set_error("%s: records not 4-byte or workspace not 8-byte aligned", fn);
+    return USF_EINVAL;
+  }
+  const long long need = hg_workspace_bytes(B, H, W, K, n_hyp);
+  if (workspace_bytes < need) {
+    set_error("%s: workspace of %lld bytes, need %lld (usf_hg_workspace_bytes)", fn, workspace_bytes, need);
+    return USF_EINVAL;
+  }
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn,
+                hg_fit_launch(flow, flow_bstride, seg, occ, K, thr, n_hyp, seed, static_cast<int*>(records), workspace,
+                              B, H, W, (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+int usf_hg_loss_partials(int B, int H, int W) {
+  if (B <= 0 || B > 65535 || H <= 0 || W <= 0 || (long long)H * W > 0x1FFFFFFFLL) return 0;
+  return hg_loss_partials(B, H, W);
+}
+
+int usf_hg_loss_fwd_f32(const float* flow, long long flow_bstride, const float* seg, const void* records,
+                        double* partials, float* out, int B, int H, int W, void* stream) {
+  clear_error();
+  const char* fn = "usf_hg_loss_fwd_f32";
+  if (!check_hg(fn, B, H, W, flow_bstride)) return USF_EINVAL;
+  if (!flow || !seg || !records) {
+    set_error("%s: null input pointer", fn);
+    return USF_EINVAL;
+  }
+  if (!partials || !out) {
+    set_error("%s: null output pointer", fn);
+    return USF_EINVAL;
+  }
+  if ((uintptr_t)records % 4 != 0 || (uintptr_t)partials % 8 != 0) {
+    set_error("%s: records not 4-byte or partials not 8-byte aligned", fn);
+    return USF_EINVAL;
+  }
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn,
+                hg_loss_fwd_launch(flow, flow_bstride, seg, static_cast<const int*>(records), partials, out, B, H, W,
+                                   (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+int usf_hg_loss_bwd_f32(const float* flow, long long flow_bstride, const float* seg, const void* records,
+                        const float* grad_loss, float* grad_flow, int B, int H, int W, void* stream) {
+  clear_error();
+  const char* fn = "usf_hg_loss_bwd_f32";
+  if (!check_hg(fn, B, H, W, flow_bstride)) return USF_EINVAL;
+  if (!flow || !seg || !records || !grad_loss) {
+    set_error("%s: null input pointer", fn);
+    return USF_EINVAL;
+  }
+  if (!grad_flow) {
+    set_error("%s: null output pointer", fn);
+    return USF_EINVAL;
+  }
+  if ((uintptr_t)records % 4 != 0) {
+    set_error("%s: records not 4-byte aligned", fn);
+    return USF_EINVAL;
+  }
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn,
+                hg_loss_bwd_launch(flow, flow_bstride, seg, static_cast<const int*>(records), grad_loss, grad_flow, B,
+                                   H, W, (hipStream_t)stream),
                 (hipStream_t)stream);
 }
 

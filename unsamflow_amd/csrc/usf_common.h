@@ -187,6 +187,18 @@ hipError_t segpool_fwd_launch(const float* proj, const float* seg, float* spread
 hipError_t segpool_bwd_launch(const float* proj, const float* seg, const unsigned* state, const float* gs, float* gp,
                               int B, int C, int H, int W, int K, hipStream_t s);
 
+// hg.hip: the homography smoothness loss (segment selection, RANSAC fit, loss)
+int hg_device_errors(bool clear);  // this code object's flags (device_errors() adds them)
+long long hg_workspace_bytes(int B, int H, int W, int K, int n_hyp);
+hipError_t hg_fit_launch(const float* flow, long long fbs, const float* seg, const float* occ, int K, float thr,
+                         int n_hyp, unsigned long long seed, int* records, void* workspace, int B, int H, int W,
+                         hipStream_t s);
+int hg_loss_partials(int B, int H, int W);
+hipError_t hg_loss_fwd_launch(const float* flow, long long fbs, const float* seg, const int* records, double* partials,
+                              float* out, int B, int H, int W, hipStream_t s);
+hipError_t hg_loss_bwd_launch(const float* flow, long long fbs, const float* seg, const int* records,
+                              const float* gloss, float* gflow, int B, int H, int W, hipStream_t s);
+
 hipError_t upsample_fwd_launch(const float* x, float* out, int B, int C, int H, int W, int k,
                                hipStream_t s);
 hipError_t upsample_bwd_launch(const float* gout, float* gx, int B, int C, int H, int W, int k,

@@ -27,6 +27,7 @@
 
 #include "interp_tap.h"
 #include "usf_common.h"
+#include "../../include/unsamflow_hip_hg.h"
 #include "../../include/unsamflow_hip_segpool.h"
 #include "warp_tap.h"
 
@@ -1583,9 +1584,10 @@ int device_errors(hipStream_t s, bool clear, int mask) {
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_dev_errors), &z, sizeof(int)) != hipSuccess) return -1;
   }
   v &= mask;
-  // segpool.hip keeps its own flag word (one code object per source file)
+  // segpool.hip and hg.hip keep their own flag words (one code object per source file)
   const int sp = (mask & USF_DEVERR_SEGPOOL_BAD_ID) ? segpool_device_errors(clear) : 0;
-  return sp < 0 ? -1 : (v | sp);
+  const int hg = (mask & USF_DEVERR_HG_BAD_ID) ? hg_device_errors(clear) : 0;
+  return (sp < 0 || hg < 0) ? -1 : (v | sp | hg);
 }
 
 hipError_t warp_fwd_launch(const float* x, const float* flow, long long fbs, float* out, int B,

@@ -17,9 +17,14 @@ its terms under one normaliser. ``fused_photometric=False`` or an injected
 ``warp_fn`` keeps the torch composition.
 Returns ``(loss[None], l_ph[None], l_sm[None], flow_mean[None], vis1, vis2)``.
 
-``smooth_type == "homography"`` needs OpenCV RANSAC on the host
-(loss_blocks.py:125-200) and is not supported (not on the hot path; the base
-configs use ``w_sm = 0``).
+``smooth_type == "homography"`` (stage 2, loss_blocks.py:125-200 and
+flow_loss.py:154-168) is unsamflow_amd.homography.smooth_homography on the
+unscaled finest flow halves with ``full_seg1`` / ``full_seg2`` and ``1 - vis``,
+averaged under ``with_bk``: on a ROCm device the segment selection, the RANSAC
+fit and the loss are HIP kernels with no host sync where the reference calls
+OpenCV per segment; ``fused_homography=False`` keeps the host loop with the
+numpy estimator. Without the ``full_seg`` kwargs it raises
+``NotImplementedError``.
 """
 from __future__ import annotations
 
@@ -109,7 +114,8 @@ PHOTO_PYRAMID = True
 
 class unFlowLoss(nn.Module):  # noqa: N801 (reference name)
     def __init__(self, cfg, warp_fn: Callable | None = None, occ_backward_fn: Callable | None = None,
-                 occ_bidir_fn: Callable | None = None, fused_photometric: bool = True):
+                 occ_bidir_fn: Callable | None = None, fused_photometric: bool = True,
+                 fused_homography: bool = True):
         super().__init__()
         self.cfg = cfg
         if "ransac_threshold" not in cfg:
@@ -120,6 +126,8 @@ class unFlowLoss(nn.Module):  # noqa: N801 (reference name)
         # fused photometric kernels only behind the library's own warp (an injected
         # warp -- e.g. the CPU oracle -- keeps the torch composition below)
         self.fused = warp_fn is None and fused_photometric
+        # the homography smoothness kernels on a ROCm device; False keeps the host loop
+        self.fused_homography = fused_homography
         self.occ_backward = occ_backward_fn or warp_utils.get_occu_mask_backward
         self.lib_occ = occ_backward_fn is None  # the library's masks: both directions in one call
         self.occ_bidir = occ_bidir_fn or (lambda f12, f21: warp_utils.get_occu_mask_bidirection(f12, f21))
@@ -169,6 +177,15 @@ class unFlowLoss(nn.Module):  # noqa: N801 (reference name)
         if "smooth_edge" not in self.cfg or self.cfg.smooth_edge == "image":
             return fn(flow, im1_scaled, edge="image", alpha=self.cfg.edge_aware_alpha).mean()
         return fn(flow, im1_scaled, edge="full_seg", full_seg=kw["full_seg"]).mean()
+
+    def loss_smooth_homography(self, flow, full_seg, vis):
+        """smooth_homography on one unscaled flow half (flow_loss.py:154-168)."""
+        from . import homography
+
+        c = self.cfg
+        fused = None if self.fused_homography else False
+        return homography.smooth_homography(flow, full_seg, 1 - vis, c.ransac_threshold,
+                                            c.num_segments if "num_segments" in c else None, fused=fused)
 
     def _image_pyramid(self, im, sizes):
         """{(h, w): F.interpolate(im, (h, w), mode="area")} for the loss scales,
@@ -273,7 +290,14 @@ class unFlowLoss(nn.Module):  # noqa: N801 (reference name)
 
             if i == 0 and c.w_sm > 0:
                 if c.smooth_type == "homography":
-                    raise NotImplementedError("homography smoothness needs OpenCV RANSAC (not on the hot path)")
+                    if kw.get("full_seg1") is None or (c.with_bk and kw.get("full_seg2") is None):
+                        raise NotImplementedError("homography smoothness needs the segment maps: pass full_seg1 "
+                                                  "(and full_seg2 under with_bk)")
+                    ls = self.loss_smooth_homography(flow[:, :2], kw["full_seg1"], vis1_pyr[0])
+                    if c.with_bk:
+                        ls = (ls + self.loss_smooth_homography(flow[:, 2:], kw["full_seg2"], vis2_pyr[0])) / 2.0
+                    smooth_losses.append(ls)
+                    continue
                 if im1_s is None:
                     im1_s = F.interpolate(im1_origin, (h, w), mode="area")
                     im2_s = F.interpolate(im2_origin, (h, w), mode="area")

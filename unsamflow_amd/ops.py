@@ -796,6 +796,89 @@ def segpool_backward(proj, seg, state, grad_spread, num_segments: int):
     return gproj
 
 
+def _hg_args(flow, seg):
+    fv, fbs, B, H, W = _flow_arg(flow, "flow")
+    _require_device_f32("full_seg", seg)
+    if tuple(seg.shape) != (B, 1, H, W) or seg.device != fv.device:
+        raise ValueError(f"full_seg must be [B,1,h,w] = {(B, 1, H, W)} on {fv.device}, got {tuple(seg.shape)}")
+    return fv, fbs, seg.contiguous(), B, H, W
+
+
+def _hg_records(records, B, dev):
+    if (not isinstance(records, torch.Tensor) or records.dtype != torch.int32 or records.device != dev
+            or tuple(records.shape) != (B, _lib.HG_SLOTS, _lib.HG_RECORD_WORDS) or not records.is_contiguous()):
+        raise ValueError(f"records must be the contiguous int32 [{B},{_lib.HG_SLOTS},{_lib.HG_RECORD_WORDS}] "
+                         f"tensor of hg_fit on {dev}")
+    return records
+
+
+def hg_fit(flow, seg, occ, num_segments: int, thr: float, n_hyp: int = _lib.HG_DEFAULT_HYP, seed: int = 0):
+    """Select the six segments per sample and fit their homographies by RANSAC
+    (include/unsamflow_hip_hg.h; loss_blocks.py:125-178). flow [B,2,h,w] (a
+    channel slice of a [B,4,h,w] tensor is read in place); seg, occ [B,1,h,w]
+    fp32 -> records, int32 [B, 6, 16] (id, status, n_seg, n_rel, n_inl, H as
+    float bits, best_j, list offset). No host sync."""
+    fv, fbs, s, B, H, W = _hg_args(flow, seg)
+    dev = fv.device
+    _require_device_f32("occ_mask", occ)
+    if tuple(occ.shape) != (B, 1, H, W) or occ.device != dev:
+        raise ValueError(f"occ_mask must be [B,1,h,w] = {(B, 1, H, W)} on {dev}, got {tuple(occ.shape)}")
+    o = occ.contiguous()
+    K, n_hyp = int(num_segments), int(n_hyp)
+    if not 1 <= K <= _lib.HG_MAX_K:
+        raise ValueError(f"num_segments={K} outside [1, {_lib.HG_MAX_K}] (USF_HG_MAX_K)")
+    lib = _lib.load()
+    nbytes = lib.usf_hg_workspace_bytes(B, H, W, K, n_hyp)
+    if nbytes <= 0:
+        raise ValueError(f"hg_fit: bad arguments B={B} H={H} W={W} K={K} n_hyp={n_hyp}")
+    ws = torch.empty(nbytes // 8, device=dev, dtype=torch.int64)
+    records = torch.empty((B, _lib.HG_SLOTS, _lib.HG_RECORD_WORDS), device=dev, dtype=torch.int32)
+    _args = (fv.data_ptr(), fbs, s.data_ptr(), o.data_ptr(), K, float(thr), n_hyp, int(seed) & (2 ** 64 - 1),
+             records.data_ptr(), ws.data_ptr(), nbytes, B, H, W, _lib.stream_handle(dev),)
+    # algorithmic bytes: seg and occ read for the statistics and the lists, flow for the pairs
+    with torch.cuda.device(dev), _kt.timed("hg_fit", (B, H, W, K, n_hyp), dev, B * H * W * 24):
+        rc = lib.usf_hg_fit_f32(*_args)
+    _lib.check(rc, "usf_hg_fit_f32")
+    return records
+
+
+def hg_loss_forward(flow, seg, records):
+    """The homography smoothness loss of given records -> a 0-d tensor: the L1
+    distance of ``p + flow`` to ``dehom(H p)`` over the accepted slots' segments
+    / (h * w * B) (loss_blocks.py:179-200)."""
+    fv, fbs, s, B, H, W = _hg_args(flow, seg)
+    dev = fv.device
+    _hg_records(records, B, dev)
+    lib = _lib.load()
+    partials = torch.empty(lib.usf_hg_loss_partials(B, H, W), device=dev, dtype=torch.float64)
+    out = torch.empty(1, device=dev, dtype=torch.float32)
+    _args = (fv.data_ptr(), fbs, s.data_ptr(), records.data_ptr(), partials.data_ptr(), out.data_ptr(), B, H, W,
+             _lib.stream_handle(dev),)
+    with torch.cuda.device(dev), _kt.timed("hg_loss_fwd", (B, H, W), dev, B * H * W * 12):
+        rc = lib.usf_hg_loss_fwd_f32(*_args)
+    _lib.check(rc, "usf_hg_loss_fwd_f32")
+    return out[0]
+
+
+def hg_loss_backward(flow, seg, records, grad_loss):
+    """d(hg_loss_forward)/d(flow) applied to the 0-d ``grad_loss`` -> [B,2,h,w]:
+    ``-sign(diff) * grad_loss / (h * w * B)`` on the accepted slots' segments."""
+    fv, fbs, s, B, H, W = _hg_args(flow, seg)
+    dev = fv.device
+    _hg_records(records, B, dev)
+    _require_device_f32("grad_loss", grad_loss)
+    if grad_loss.numel() != 1 or grad_loss.device != dev:
+        raise ValueError("grad_loss must be one float32 on the flow's device")
+    g = grad_loss.contiguous()
+    gflow = torch.empty((B, 2, H, W), device=dev, dtype=torch.float32)
+    _args = (fv.data_ptr(), fbs, s.data_ptr(), records.data_ptr(), g.data_ptr(), gflow.data_ptr(), B, H, W,
+             _lib.stream_handle(dev),)
+    with torch.cuda.device(dev), _kt.timed("hg_loss_bwd", (B, H, W), dev, B * H * W * 20):
+        rc = _lib.load().usf_hg_loss_bwd_f32(*_args)
+    _lib.check(rc, "usf_hg_loss_bwd_f32")
+    return gflow
+
+
 def device_errors(device, clear: bool = True) -> int:
     """The USF_DEVERR_* flags kernels raised on ``device``'s current stream since
     the last clear (usf_device_errors; synchronises the stream)."""
