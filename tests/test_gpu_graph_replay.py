@@ -26,7 +26,8 @@ def _replayed(fn, reps=4):
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
+    hold = ops.WorkspaceHold()  # the persistent workspaces that fn uses live as long as this graph
+    with hold, torch.cuda.graph(graph):
         out = fn()
     results = []
     for _ in range(reps):
@@ -34,6 +35,7 @@ def _replayed(fn, reps=4):
         torch.cuda.synchronize()
         results.append([None if t is None else t.clone() for t in out])
     del graph
+    hold.release()
     return results
 
 

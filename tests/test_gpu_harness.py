@@ -70,7 +70,12 @@ def test_train_step_full_kitti_size(hip_device):
 def test_graphed_step_matches_eager_steps(hip_device):
     """harness.GraphedTrainStep (the step captured into a HIP graph and replayed)
     trains like TrainStep: same losses and parameters after the same number of
-    steps from the same state (up to the warp backward's atomic summation order)."""
+    steps from the same state (up to the warp backward's atomic summation order).
+    Between the two replays the persistent workspaces that the graph recorded
+    are pushed out of ops' cache (more than its bound of other shapes, then a
+    clear): the graph's own hold keeps them allocated, so the second replay
+    still trains like the eager step."""
+    from persist_util import cache_pressure
     from oracle.hashrng import uniform
     from unsamflow_amd.config import kitti_base
     from unsamflow_amd.harness import GraphedTrainStep, TrainStep
@@ -81,7 +86,10 @@ def test_graphed_step_matches_eager_steps(hip_device):
     graphed = TrainStep(kitti_base(), hip_device, capturable=True)
     losses_e = [float(eager(im1, im2)) for _ in range(3)]
     g = GraphedTrainStep(graphed, im1, im2, warmup=1)  # 1 eager warm-up step, then capture
-    losses_g = [float(g()) for _ in range(2)]
+    losses_g = [float(g())]
+    assert len(g.workspaces) > 0  # the step's warp backward and occlusion workspaces
+    cache_pressure(hip_device)
+    losses_g.append(float(g()))
     torch.cuda.synchronize()
     # the graph's first replay is step 2 (the warm-up was step 1)
     np.testing.assert_allclose(losses_g, losses_e[1:], rtol=1e-4)
@@ -89,3 +97,4 @@ def test_graphed_step_matches_eager_steps(hip_device):
         torch.testing.assert_close(pg, pe, atol=1e-5, rtol=1e-4, msg=n)
     assert float(graphed.optimizer.param_groups[0]["lr"]) == pytest.approx(
         float(eager.optimizer.param_groups[0]["lr"]))
+    g.release()

@@ -14,6 +14,7 @@ within atol 1e-5 where overflow entries are summed by fp32 atomics
 import pytest
 import torch
 
+from persist_util import np_fields as _np_fields
 from unsamflow_amd import _lib, ops
 
 pytestmark = pytest.mark.gpu
@@ -155,24 +156,6 @@ def test_occ_persist_call_sequence_matches_per_call_form(hip_device):
             assert int(torch.count_nonzero(ws)) == 0, key  # the threshold pass left every map zero
 
 
-def _np_fields(B, H, W):
-    """Decoder-style flows as numpy: a smooth +-2 px field with a per-sample
-    phase, a border-piling shift (a strip of sources clamped onto the edge
-    column: many pixels per cell), and a field contracting towards the centre
-    (whole regions share a cell: overflow entries and dirty tiles)."""
-    import numpy as np
-
-    yy, xx = np.meshgrid(np.arange(H, dtype=np.float32), np.arange(W, dtype=np.float32), indexing="ij")
-    ph = np.arange(B, dtype=np.float32).reshape(B, 1, 1) * 0.7
-    u = np.sin(2 * np.pi * 2 * xx / W + ph) + np.cos(2 * np.pi * 3 * yy / H - ph)
-    v = np.cos(2 * np.pi * 2 * xx / W - ph) - np.sin(2 * np.pi * 3 * yy / H + ph)
-    smooth = np.stack([u, v], 1).astype(np.float32)
-    pile = smooth.copy()
-    pile[:, 0] += W / 8.0
-    contract = np.stack([0.9 * ((W - 1) / 2.0 - xx), 0.9 * ((H - 1) / 2.0 - yy)])[None].repeat(B, 0)
-    return {"smooth": smooth, "pile": pile, "contract": contract.astype(np.float32)}
-
-
 @pytest.mark.parametrize("form", ["production", "persist"])
 @pytest.mark.parametrize("pad", ["border", "zeros"])
 @pytest.mark.parametrize("shape", [(16, 128, 8, 26), (16, 96, 16, 52), (16, 64, 32, 104), (16, 32, 64, 208)])
@@ -212,8 +195,18 @@ def test_warp_persist_production_shapes_vs_oracle(hip_device, shape, pad, form, 
 def test_persistent_workspace_cache_is_bounded_and_ordered(hip_device, monkeypatch):
     """the cache keeps at most PERSIST_MAX_ENTRIES shapes (least
     recently used out), and a use from another stream is ordered after the
-    previous one (the new stream waits for the owning stream)."""
+    previous one (the new stream waits for the owning stream). A use on a
+    stream other than the allocation stream is reported to the caching
+    allocator (Tensor.record_stream), a use on the allocation stream is not."""
     monkeypatch.setattr(ops, "WARP_PERSIST_MAX_PIXELS", None)
+    told = []  # (address, stream) of every record_stream call
+    record_stream = torch.Tensor.record_stream
+
+    def spy(self, stream):
+        told.append((self.data_ptr(), stream))
+        return record_stream(self, stream)
+
+    monkeypatch.setattr(torch.Tensor, "record_stream", spy)
     ops.clear_persistent_workspaces()
     for i in range(ops.PERSIST_MAX_ENTRIES + 5):
         ops.persistent_workspace(hip_device, "test_op", (i,), 64)
@@ -226,13 +219,20 @@ def test_persistent_workspace_cache_is_bounded_and_ordered(hip_device, monkeypat
     go = torch.randn(B, C, H, W, device=hip_device, generator=gen)
     f = _fields(B, H, W, hip_device)
     ref = ops.warp_backward(x, f["contract"], go, "border")
+    ref2 = ops.warp_backward(x, f["contract"], go, "border")
+    assert told == []  # created and used on the main stream: nothing to tell the allocator
+    ptr = ops._PERSIST[(hip_device.index, "warp_bwd", (B, C, H, W))][0].data_ptr()
     side = torch.cuda.Stream(hip_device)
     side.wait_stream(torch.cuda.current_stream(hip_device))
     with torch.cuda.stream(side):
         a = ops.warp_backward(x, f["contract"], go, "border")
         assert ops._PERSIST[(hip_device.index, "warp_bwd", (B, C, H, W))][1] == side
+        assert told == [(ptr, side)]  # the use on the side stream is known to the allocator
     b = ops.warp_backward(x, f["contract"], go, "border")  # main stream again: waits for the side stream
+    assert [t for t in told if t[1] != side] == []  # back on the allocation stream: not told
     torch.cuda.synchronize()
+    for r, s in zip(ref, ref2):
+        torch.testing.assert_close(s, r, atol=1e-5, rtol=1e-5)
     for r, s1, s2 in zip(ref, a, b):
         torch.testing.assert_close(s1, r, atol=1e-5, rtol=1e-5)
         torch.testing.assert_close(s2, r, atol=1e-5, rtol=1e-5)

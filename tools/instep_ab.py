@@ -69,7 +69,9 @@ def main():
     def use(cfg):
         lp, name, val = cfg
         torch.cuda.synchronize()
-        ops.clear_persistent_workspaces()  # layouts may differ between builds
+        # layouts may differ between builds; the steps here run eagerly, so no graph holds a
+        # workspace and the plain clear (which keeps held ones allocated) releases them all
+        ops.clear_persistent_workspaces()
         _lib._lib = handles[lp]
         if name:  # an ops global, or module.NAME of another unsamflow_amd module
             mod, _, attr = name.rpartition(".")

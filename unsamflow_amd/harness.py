@@ -236,6 +236,8 @@ class GraphedTrainStep:
                  group=None):
         import torch.distributed as dist
 
+        from . import ops
+
         if getattr(step, "has_ar", False):
             raise NotImplementedError("GraphedTrainStep: the stage-1 augmentation branch (run_atst / run_ot) is not "
                                       "capturable (the crop offsets move pointers, the thetas are sampled on the host)")
@@ -255,19 +257,31 @@ class GraphedTrainStep:
                 self.step.scheduler.step()
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
+        # the graphs record the raw addresses of the persistent workspaces the
+        # warm-up created (warp backward, occlusion maps): this hold keeps those
+        # tensors allocated for as long as the graphs can be replayed
+        self.workspaces = ops.WorkspaceHold()
         if self.world == 1:
             self.graph_a = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph_a):
+            with self.workspaces, torch.cuda.graph(self.graph_a):
                 self.loss = self._fwd_bwd()
                 self._update()
             self.graph_b = None
         else:
             self.graph_a = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph_a):
+            with self.workspaces, torch.cuda.graph(self.graph_a):
                 self.loss = self._fwd_bwd()
             self.graph_b = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph_b, pool=self.graph_a.pool()):
+            with self.workspaces, torch.cuda.graph(self.graph_b, pool=self.graph_a.pool()):
                 self._update()
+
+    def release(self):
+        """Delete the graphs and release the persistent workspaces they
+        recorded. Call it on the stream the step was replayed on; the step
+        cannot be called afterwards. An object that is merely dropped frees
+        them too, with its hold: do that only once its replays have finished."""
+        self.graph_a = self.graph_b = None
+        self.workspaces.release()
 
     def _fwd_bwd(self):
         self.grads.zero_()
@@ -289,6 +303,8 @@ class GraphedTrainStep:
                 dst.copy_(src)
 
     def __call__(self):
+        if self.graph_a is None:
+            raise RuntimeError("GraphedTrainStep: called after release()")
         self.graph_a.replay()
         if self.graph_b is not None:
             self._reduce()

@@ -331,7 +331,13 @@ def device_time_cold_us(fn, reps: int = 8, flush_mib: int = 512) -> float:
 
 
 def device_time_us(fn, reps: int = 20, iters: int = 5) -> float:
-    """Mean device time of one ``fn()`` launch: REPS launches in a HIP graph, replayed."""
+    """Mean device time of one ``fn()`` launch: REPS launches in a HIP graph, replayed.
+
+    The persistent workspaces that ``fn`` uses are held for this graph alone
+    (ops.WorkspaceHold) and released with it, so a sweep over many shapes keeps
+    no more of them than the cache's bound."""
+    from . import ops
+
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
@@ -340,18 +346,22 @@ def device_time_us(fn, reps: int = 20, iters: int = 5) -> float:
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        for _ in range(reps):
-            fn()
-    graph.replay()
-    torch.cuda.synchronize()
-    s = torch.cuda.Event(enable_timing=True)
-    e = torch.cuda.Event(enable_timing=True)
-    s.record()
-    for _ in range(iters):
+    hold = ops.WorkspaceHold()
+    try:
+        with hold, torch.cuda.graph(graph):
+            for _ in range(reps):
+                fn()
         graph.replay()
-    e.record()
-    e.synchronize()
-    us = s.elapsed_time(e) * 1e3 / (iters * reps)
-    del graph
+        torch.cuda.synchronize()
+        s = torch.cuda.Event(enable_timing=True)
+        e = torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(iters):
+            graph.replay()
+        e.record()
+        e.synchronize()
+        us = s.elapsed_time(e) * 1e3 / (iters * reps)
+    finally:
+        del graph
+        hold.release()
     return us

@@ -8,6 +8,7 @@ CPU path: CPU tensors raise ``RuntimeError``.
 from __future__ import annotations
 
 import ctypes
+import weakref
 
 import torch
 
@@ -175,32 +176,127 @@ def warp_forward(x: torch.Tensor, flow: torch.Tensor, pad: str = "border") -> to
 # occlusion splat map) must see its calls in order, so each entry records the
 # stream of its last eager use, and a call from another stream first makes its
 # stream wait for that one (torch's wait_stream): two streams can never race a
-# workspace. A HIP graph capture reuses the workspace its eager warm-up created
-# (torch captures on its own stream; the capture records no fill, and replays
-# are uses on the replaying stream). The cache is bounded (least recently used
-# out): each warp entry holds ~88 B per pixel plus one float per element of x,
-# each occlusion entry 4 B per pixel, and a training run with a changing shape
-# (a partial last batch, evaluation at another resolution) must not keep every
-# shape's buffers alive. A call that fails drops its entry (its state may be
-# half-updated): the next call of that shape starts from a fresh zeroed buffer.
-_PERSIST: "OrderedDict[tuple, list]" = OrderedDict()
+# workspace. An entry also remembers the stream it was allocated on: a use on
+# any other stream is reported to the caching allocator (Tensor.record_stream,
+# once per stream), so that a later free cannot hand the block out on the
+# allocation stream while the other stream's kernels may still run.
+#
+# The cache is bounded (least recently used out): each warp entry holds ~88 B
+# per pixel plus one float per element of x (up to 8192 pixels; one int per
+# pixel above), each occlusion entry 4 B per pixel (8 B for the pair), and a
+# training run with a changing shape (a partial last batch, evaluation at
+# another resolution) must not keep every shape's buffers alive.
+#
+# A HIP graph capture reuses the workspace its eager warm-up created (torch
+# captures on its own stream; the capture records no fill, and replays are uses
+# on the replaying stream). The graph holds only the raw address, so a use
+# while the current stream is capturing also takes a strong reference to the
+# tensor into a WorkspaceHold: the innermost ``with WorkspaceHold()`` block, or,
+# for a bare torch.cuda.graph(...), a module-level hold that lives as long as
+# the process (that costs the entry's size per captured shape, see above, until
+# clear_persistent_workspaces(release_held=True)). Eviction, _drop_workspace and
+# clear_persistent_workspaces() only detach a held workspace from the cache: it
+# stays allocated at its address until every hold on it is released
+# (GraphedTrainStep.release(), kernel_timer.device_time_us per timed site).
+#
+# A call that fails drops its entry (its state may be half-updated): the next
+# call of that shape starts from a fresh zeroed buffer. If the entry is held,
+# a graph still replays into it, so it is not freed: it is zero-filled in
+# stream order (zeros is the state a fresh entry starts from; the kernels read
+# their parity from the device header) and detached from the cache.
+class _Entry(list):
+    """``[workspace, stream of its last eager use]`` of one cache slot, plus the
+    stream the workspace was allocated on and the other streams the allocator
+    has been told about."""
+    __slots__ = ("alloc_stream", "recorded")
+
+    def __init__(self, ws, stream):
+        super().__init__((ws, stream))
+        self.alloc_stream = stream
+        self.recorded = set()
+
+    def used_on(self, stream) -> None:
+        """Tell the allocator that the workspace is used on ``stream``."""
+        if stream != self.alloc_stream and stream not in self.recorded:
+            self[0].record_stream(stream)
+            self.recorded.add(stream)
+
+
+class WorkspaceHold:
+    """Strong references to the persistent workspaces that HIP graphs recorded.
+
+    ``with hold, torch.cuda.graph(g): ...`` files every workspace that a
+    persistent op uses during the capture under ``hold``; keep the hold next to
+    the graph and call :meth:`release` when the graph goes away (on the stream
+    the graph was replayed on). Until then the workspaces stay allocated at the
+    captured addresses, whatever happens to the cache."""
+
+    def __init__(self):
+        self._held: dict[int, _Entry] = {}
+        _HOLDS.add(self)
+
+    def __enter__(self):
+        _HOLD_STACK.append(self)
+        return self
+
+    def __exit__(self, *exc):
+        _HOLD_STACK.remove(self)
+        return False
+
+    def __len__(self):
+        return len(self._held)
+
+    def _add(self, ent: _Entry) -> None:
+        self._held[id(ent)] = ent
+
+    def holds(self, ent: _Entry) -> bool:
+        return id(ent) in self._held
+
+    def release(self) -> None:
+        """Drop the references. The graphs that recorded these workspaces must
+        not be replayed again. The replays issued so far are taken to be on the
+        current stream: the allocator is told so, and a workspace freed here is
+        not handed out before they finish."""
+        for ent in self._held.values():
+            if not torch.cuda.is_current_stream_capturing():
+                ent.used_on(torch.cuda.current_stream(ent[0].device))
+        self._held.clear()
+
+
+_PERSIST: "OrderedDict[tuple, _Entry]" = OrderedDict()
 PERSIST_MAX_ENTRIES = 32
+_HOLDS: "weakref.WeakSet[WorkspaceHold]" = weakref.WeakSet()
+_HOLD_STACK: "list[WorkspaceHold]" = []  # the open ``with WorkspaceHold()`` blocks, innermost last
+_PROCESS_HOLD = WorkspaceHold()  # captures outside any such block
+
+
+def _is_held(ent: _Entry) -> bool:
+    return any(h.holds(ent) for h in _HOLDS)
 
 
 def persistent_workspace(device: torch.device, op: str, shape: tuple, nbytes: int) -> torch.Tensor:
     """The zero-initialised persistent workspace of ``op`` at ``shape`` on
     ``device``, ordered after its previous use (created on first use with
-    torch.zeros on the current stream, so the zeroing precedes the first call)."""
+    torch.zeros on the current stream, so the zeroing precedes the first call).
+
+    A use on a stream other than the one it was allocated on is recorded with
+    the caching allocator. A use while the current stream is capturing a HIP
+    graph puts the tensor into the innermost open :class:`WorkspaceHold`, or
+    into the process-lifetime hold: the graph's address stays valid after
+    eviction, :func:`_drop_workspace` and :func:`clear_persistent_workspaces`."""
     key = (device.index, op, tuple(shape))
     cur = torch.cuda.current_stream(device)
     capturing = torch.cuda.is_current_stream_capturing()
     ent = _PERSIST.get(key)
     if ent is not None and ent[0].numel() >= nbytes:
         _PERSIST.move_to_end(key)
-        if not capturing:
+        if capturing:
+            (_HOLD_STACK[-1] if _HOLD_STACK else _PROCESS_HOLD)._add(ent)
+        else:
             if ent[1] != cur:
                 cur.wait_stream(ent[1])  # the previous use on another stream comes first
-            ent[1] = cur
+                ent[1] = cur
+                ent.used_on(cur)  # every use off the allocation stream follows a switch to it
         return ent[0]
     if capturing:
         # torch.zeros inside a capture is only recorded: the eager calls after it
@@ -209,19 +305,41 @@ def persistent_workspace(device: torch.device, op: str, shape: tuple, nbytes: in
             f"unsamflow_amd: first use of the persistent {op} workspace for shape {tuple(shape)} inside a "
             "HIP graph capture; run the call once eagerly before capturing")
     ws = torch.zeros(nbytes, device=device, dtype=torch.uint8)
-    _PERSIST[key] = [ws, cur]
+    _PERSIST[key] = _Entry(ws, cur)
     while len(_PERSIST) > PERSIST_MAX_ENTRIES:
         _PERSIST.popitem(last=False)
     return ws
 
 
 def _drop_workspace(device: torch.device, op: str, shape: tuple) -> None:
-    _PERSIST.pop((device.index, op, tuple(shape)), None)
+    """Detach the entry of a failed call from the cache. Not held: it is freed.
+    Held by a capture: it stays allocated and is put back to its initial state,
+    zero-filled on the current stream after its last eager use (nothing ran if
+    the failure happened inside a capture, so nothing is filled then)."""
+    ent = _PERSIST.pop((device.index, op, tuple(shape)), None)
+    if ent is None or not _is_held(ent) or torch.cuda.is_current_stream_capturing():
+        return
+    cur = torch.cuda.current_stream(device)
+    if ent[1] != cur:
+        cur.wait_stream(ent[1])
+    ent[1] = cur
+    ent.used_on(cur)
+    ent[0].zero_()
 
 
-def clear_persistent_workspaces() -> None:
-    """Release every persistent workspace (the next call of each shape re-creates it)."""
+def clear_persistent_workspaces(release_held: bool = False) -> None:
+    """Empty the cache: every workspace that no capture holds is released, and
+    the next call of each shape re-creates it. A workspace held for a HIP graph
+    (:class:`WorkspaceHold`) only leaves the cache and stays allocated.
+
+    ``release_held=True`` also releases every live hold, the process-lifetime
+    one included. THIS INVALIDATES LIVE GRAPHS: a graph that recorded one of
+    these workspaces must never be replayed afterwards (its replay would write
+    into memory that may belong to another tensor)."""
     _PERSIST.clear()
+    if release_held:
+        for h in list(_HOLDS):
+            h.release()
 
 
 # The largest level (H*W pixels) that takes the persistent warp backward
@@ -255,8 +373,10 @@ def warp_backward(
     pixels (strongly compressive flow), whose excess is added with fp32
     atomics. Its workspace (``usf_warp_bwd_persist_workspace``: ~88 B per pixel,
     plus one float per element of x up to 8192 pixels, one int per pixel above)
-    is kept per (device, shape) and ordered
-    across streams (:func:`persistent_workspace`). grad_flow is deterministic."""
+    is kept per (device, shape), ordered across streams and, when the call is
+    captured into a HIP graph, kept allocated for that graph
+    (:func:`persistent_workspace`, :class:`WorkspaceHold`). grad_flow is
+    deterministic."""
     _require_device_f32("x", x)
     _require_device_f32("flow12", flow)
     _require_device_f32("grad_output", grad_out)
@@ -325,7 +445,11 @@ def splat_map(flow: torch.Tensor, absolute: bool = False) -> torch.Tensor:
 
 
 def occ_backward(flow21: torch.Tensor, th: float = 0.2) -> torch.Tensor:
-    """Occlusion mask get_occu_mask_backward (warp_utils.py:120-126) -> [B,1,H,W] float."""
+    """Occlusion mask get_occu_mask_backward (warp_utils.py:120-126) -> [B,1,H,W] float.
+
+    The splat map is a persistent workspace per (device, B, H, W): ordered
+    across streams, and held for the graph when the call is captured
+    (:func:`persistent_workspace`, :class:`WorkspaceHold`)."""
     fv, fbs, B, H, W = _flow_arg(flow21, "flow21")
     out = torch.empty((B, 1, H, W), device=flow21.device, dtype=torch.float32)
     lib = _lib.load()
@@ -350,7 +474,9 @@ def occ_vis_pair(flow4: torch.Tensor, th: float = 0.2) -> torch.Tensor:
     get_occu_mask_backward(flow4[:, :2], th)`` -> [2,B,1,H,W] (each half a
     contiguous [B,1,H,W]): one splat launch over both flow halves into a
     persistent interleaved map and one threshold pass (usf_occ_vis_pair_persist_f32)
-    instead of two splats, two thresholds and two ``1 - occ`` passes."""
+    instead of two splats, two thresholds and two ``1 - occ`` passes. The map is
+    a persistent workspace like :func:`occ_backward`'s: ordered across streams,
+    and held for the graph when the call is captured (:class:`WorkspaceHold`)."""
     _require_device_f32("flow4", flow4)
     if flow4.dim() != 4 or flow4.shape[1] != 4:
         raise ValueError(f"flow4 must be [B,4,H,W], got {tuple(flow4.shape)}")
