@@ -85,3 +85,19 @@ def test_lds_dma_hazard_checker_flags_an_unpadded_dma():
                (0xC, "s_nop", "0"), (0x10, "s_add_u32", "s2, s2, 1"), (0x14, "s_add_u32", "s2, s2, 1"),
                (0x18, dma[1], dma[2])]
     assert t.analyze(branchy)[1]
+
+
+def test_every_included_header_and_source_is_listed_in_the_build():
+    """build_id() and the staleness check only see build.SOURCES / HEADERS /
+    PUBLIC_HEADERS: a header included but not listed would drop out of both."""
+    from unsamflow_amd import build
+
+    csrc = REPO / "unsamflow_amd" / "csrc"
+    listed = set(build.HEADERS) | set(build.PUBLIC_HEADERS)
+    files = [f for f in sorted(csrc.iterdir()) if f.suffix in (".hip", ".cpp", ".h")]
+    assert files
+    for f in files:
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read_text(), re.M):
+            assert inc.rsplit("/", 1)[-1] in listed, f"{f.name} includes {inc}, which the build does not list"
+    assert {f.name for f in files if f.suffix == ".hip"} <= set(build.SOURCES)
+    assert {f.name for f in files if f.suffix == ".h"} == set(build.HEADERS)

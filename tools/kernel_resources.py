@@ -36,7 +36,7 @@ def resources(src):
 
 
 if __name__ == "__main__":
-    srcs = sys.argv[1:] or [REPO / "unsamflow_amd/csrc/corr.hip", REPO / "unsamflow_amd/csrc/warp.hip"]
+    srcs = sys.argv[1:] or [REPO / "unsamflow_amd/csrc" / f for f in ("corr.hip", "warp.hip", "occ.hip")]
     for src in srcs:
         for name, v, lds, scratch in resources(src):
             wps = min(8, 512 // (((v + 7) // 8) * 8))

@@ -1,17 +1,13 @@
-// Unit probe for warp.hip's wave-level reduce-by-key helpers (row_runs,
-// run_sum): one wave per test vector; dumps pos/maxlen/tail/take/give and the
-// run sums per lane for comparison with a Python model (tools/gpu_runs_probe.sh).
+// Unit probe for the wave-level reduce-by-key helpers (row_runs in
+// csrc/scatter_rows.h, run_sum in csrc/wave.h): one wave per test vector; dumps
+// pos/maxlen/tail/take/give and the run sums per lane for comparison with a
+// Python model.
+// Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -Iinclude -o tools/probes/runs_probe tools/probes/runs_probe.hip
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
-#include "../../unsamflow_amd/csrc/warp.hip"
-
-namespace usf {
-void set_error(const char*, ...) {}
-void clear_error() {}
-int variant_override(int) { return -1; }
-}  // namespace usf
+#include "../../unsamflow_amd/csrc/scatter_rows.h"
 
 __global__ void probe(const int* keys, const int* mw, const int* me, const int* hl, const int* hr,
                       const float* v, int* out_i, float* out_f) {

@@ -24,8 +24,8 @@ INCLUDE_DIR = PKG_DIR.parent / "include"
 ARCH = os.environ.get("USF_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-SOURCES = ["corr.hip", "warp.hip", "photo.hip", "census.hip", "ar.hip", "segpool.hip", "hg.hip", "upsample.hip", "convex.hip", "stream.hip", "capi.cpp"]
-HEADERS = ["usf_common.h", "warp_tap.h", "interp_tap.h", "strip.h"]
+SOURCES = ["corr.hip", "warp.hip", "occ.hip", "photo.hip", "census.hip", "ar.hip", "segpool.hip", "hg.hip", "upsample.hip", "convex.hip", "stream.hip", "capi.cpp"]
+HEADERS = ["usf_common.h", "warp_tap.h", "interp_tap.h", "strip.h", "wave.h", "scatter_rows.h", "seg_key.h"]
 PUBLIC_HEADERS = ["unsamflow_hip.h", "unsamflow_hip_census.h", "unsamflow_hip_ar.h", "unsamflow_hip_segpool.h",
                   "unsamflow_hip_hg.h"]  # the C ABI (include/)
 

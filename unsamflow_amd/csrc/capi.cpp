@@ -1,5 +1,6 @@
 // C ABI of libunsamflow_hip.so (declared in include/unsamflow_hip.h).
-// Argument validation + error reporting; the launches live in corr.hip / warp.hip.
+// Argument validation + error reporting; the launches live in the .hip files
+// beside it (usf_common.h declares them, grouped by file).
 #include <hip/hip_runtime.h>
 
 #include <climits>

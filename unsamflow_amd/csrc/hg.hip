@@ -30,7 +30,9 @@
 // finalisation; its backward recomputes diff from flow, seg and the records.
 #include <algorithm>
 
+#include "seg_key.h"
 #include "usf_common.h"
+#include "wave.h"
 
 #include "../../include/unsamflow_hip_hg.h"
 
@@ -58,13 +60,6 @@ static_assert(USF_HG_MAX_K <= 4 * kSelNT, "selection keeps four candidate ids pe
 // bad segment ids seen by this code object's kernels (usf_device_errors)
 __device__ int g_hg_errors = 0;
 
-// id of a pixel, -1 for anything that is not an integer in [0, K)
-__device__ __forceinline__ int seg_key(float s, int K) {
-  if (!(s >= 0.f && s < (float)K)) return -1;
-  const int k = (int)s;
-  return (float)k == s ? k : -1;
-}
-
 __device__ __forceinline__ float quiet_nan() { return __uint_as_float(0x7fc00000u); }
 
 // the pair of pixel p: pts1 = (x, y), pts2 = pts1 + flow, fp32 as the reference forms them
@@ -80,15 +75,6 @@ __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long x) {
-#pragma unroll
-  for (int sh = 32; sh > 0; sh >>= 1) {
-    const unsigned long long o = (unsigned long long)__shfl_xor((long long)x, sh);
-    x = o > x ? o : x;
-  }
-  return x;
 }
 
 // maximum of x over the workgroup, in every thread; red: NT / 64 words
@@ -719,13 +705,7 @@ int loss_chunks(int HW) { return (HW + kLossNT * kLossPix - 1) / (kLossNT * kLos
 }  // namespace
 
 int hg_device_errors(bool clear) {
-  int v = 0;
-  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_hg_errors), sizeof(int)) != hipSuccess) return -1;
-  if (clear && v != 0) {
-    const int z = 0;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_hg_errors), &z, sizeof(int)) != hipSuccess) return -1;
-  }
-  return v;
+  return read_clear_flags(HIP_SYMBOL(g_hg_errors), clear);
 }
 
 long long hg_workspace_bytes(int B, int H, int W, int K, int n_hyp) { return layout(B, H * W, K, n_hyp).words * 4; }

@@ -44,6 +44,7 @@
 #include "strip.h"
 #include "usf_common.h"
 #include "warp_tap.h"
+#include "wave.h"
 
 namespace usf {
 namespace {

@@ -21,14 +21,16 @@
 //
 // Backward: one workgroup per (sample, channel) walks the plane in row order.
 // Every 64-pixel step reduces grad_spread by key with the segmented shuffle
-// scan of warp.hip (row_runs / run_sum) and adds the runs to the wave's own LDS
+// scan of wave.h (wave_runs / run_sum) and adds the runs to the wave's own LDS
 // bins one after another in lane order; the waves' bins are combined in wave
 // order. The float sum G therefore has one fixed summation order and no float
 // atomics. The tie count t is an integer LDS atomic. The same workgroup then
 // re-walks the plane (L2-resident: 112 KB at Sintel L4) and writes grad_proj.
 #include <algorithm>
 
+#include "seg_key.h"
 #include "usf_common.h"
+#include "wave.h"
 
 #include "../../include/unsamflow_hip_segpool.h"
 
@@ -64,32 +66,9 @@ __device__ __forceinline__ float pooled_value(unsigned e, int n_in, int HW) {
   return m > 0.f ? m : 0.f;
 }
 
-// id of a pixel, -1 for anything that is not an integer in [0, K)
-__device__ __forceinline__ int seg_key(float s, int K) {
-  if (!(s >= 0.f && s < (float)K)) return -1;
-  const int k = (int)s;
-  return (float)k == s ? k : -1;
-}
-
-template <int CTRL>
-__device__ __forceinline__ unsigned dpp_u32(unsigned x) {
-  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, false);
-}
-
-// maximum over the 64 lanes, in every lane; all lanes must be active
-__device__ __forceinline__ unsigned wave_max_u32(unsigned x) {
-  x = max(x, dpp_u32<0xB1>(x));   // quad_perm [1,0,3,2]
-  x = max(x, dpp_u32<0x4E>(x));   // quad_perm [2,3,0,1]
-  x = max(x, dpp_u32<0x141>(x));  // row_half_mirror
-  x = max(x, dpp_u32<0x140>(x));  // row_mirror
-  x = max(x, (unsigned)__shfl_xor((int)x, 16));
-  x = max(x, (unsigned)__shfl_xor((int)x, 32));
-  return x;
-}
-
 // ---------------------------------------------------------------- forward --
 // the tables' zero fill as a kernel: a hipMemsetAsync node raced the kernel after
-// it on graph replay (warp.hip's zero_fill has the history)
+// it on graph replay (zero_fill_kernel in warp.hip has the history)
 __global__ __launch_bounds__(256) void seg_clear_kernel(unsigned* __restrict__ state, long long n) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) state[i] = 0u;
 }
@@ -238,7 +217,6 @@ __global__ __launch_bounds__(kBwdNT) void seg_bwd_kernel(const float* __restrict
   const float* x = proj + plane;
   const float* g = gs + plane;
   float* mybin = bins + wave * K;
-  const unsigned long long upto = lane == 63 ? ~0ull : ((2ull << lane) - 1);
   for (int p0 = wave * 64; p0 < HW; p0 += kBwdNT) {
     const int p = p0 + lane;
     const bool valid = p < HW;
@@ -247,17 +225,10 @@ __global__ __launch_bounds__(kBwdNT) void seg_bwd_kernel(const float* __restrict
     if (key >= 0 && x[p] == pv[key]) atomicAdd(&tcnt[key], 1);
     // runs of equal ids in lane order (every shuffle runs in all lanes)
     const int kl = __shfl_up(key, 1);
-    const bool head = lane == 0 || kl != key;
-    const unsigned long long heads = __ballot(head);
-    const int pos = lane - (63 - __clzll((long long)(heads & upto)));
-    const bool tail = lane == 63 || ((heads >> (lane + 1)) & 1ull) != 0;
-    const int maxlen = (int)wave_max_u32((unsigned)pos) + 1;
-    for (int d = 1; d < maxlen; d <<= 1) {  // segmented inclusive scan
-      const float u = __shfl_up(v, d);
-      if (pos >= d) v += u;
-    }
+    const WaveRuns r = wave_runs<true>(lane == 0 || kl != key);
+    v = run_sum(v, r);
     // one run after another: two runs of a step may carry the same id
-    unsigned long long tails = __ballot(tail && key >= 0);
+    unsigned long long tails = __ballot(r.tail && key >= 0);
     while (tails) {
       const int l = __ffsll((long long)tails) - 1;
       if (lane == l) mybin[key] += v;
@@ -288,13 +259,7 @@ int fwd_channels_per_group(int C, int K) { return std::max(1, std::min(std::min(
 }  // namespace
 
 int segpool_device_errors(bool clear) {
-  int v = 0;
-  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_seg_errors), sizeof(int)) != hipSuccess) return -1;
-  if (clear && v != 0) {
-    const int z = 0;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_seg_errors), &z, sizeof(int)) != hipSuccess) return -1;
-  }
-  return v;
+  return read_clear_flags(HIP_SYMBOL(g_seg_errors), clear);
 }
 
 long long segpool_state_words(int B, int C, int K) { return (long long)B * C * K + (long long)B * K; }

@@ -26,11 +26,6 @@ __device__ __forceinline__ float from_next(float v) {
 __device__ __forceinline__ float from_prev(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x138, 0xf, 0xf, true));
 }
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
-  return v;
-}
 
 // Scale s owns workgroups [start[s], start[s + 1]) -- the largest scale first,
 // so the small scales' few strips fill the chip's tail instead of each paying a

@@ -12,6 +12,18 @@ namespace usf {
 // stream sync; -1 if the sync or the copy failed. Only the flags in `mask` are
 // reported and cleared.
 int device_errors(hipStream_t s, bool clear, int mask = ~0);
+// One code object's flag word (a __device__ int per source file: no relocatable
+// device code): its flags in `mask`, cleared when `clear`; -1 if a copy failed.
+template <class Sym>
+int read_clear_flags(const Sym& word, bool clear, int mask = ~0) {
+  int v = 0;
+  if (hipMemcpyFromSymbol(&v, word, sizeof(int)) != hipSuccess) return -1;
+  if (clear && (v & mask) != 0) {
+    const int z = v & ~mask;
+    if (hipMemcpyToSymbol(word, &z, sizeof(int)) != hipSuccess) return -1;
+  }
+  return v & mask;
+}
 
 // Thread-local error slot behind usf_last_error_string().
 void set_error(const char* fmt, ...);
@@ -59,9 +71,9 @@ __device__ __forceinline__ int linear_block() {
   return blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
 }
 
-// Launchers implemented in corr.hip / warp.hip. They assume validated
-// arguments (capi.cpp checks shapes, d and pointers) and return the
-// hipError_t of the launch.
+// Launchers implemented in the .hip files (corr.hip, warp.hip, occ.hip and the
+// files named below). They assume validated arguments (capi.cpp checks shapes,
+// d and pointers) and return the hipError_t of the launch.
 // Correlation epilogues: output / gradient batch strides (elements; a channel
 // slice of a concat buffer) and an optional LeakyReLU (act = 1, slope).
 struct FwdEpi {
@@ -118,7 +130,10 @@ long long warp_bwd_persist_workspace(int B, int C, int H, int W);
 // the splat map zero)
 hipError_t warp_persist_check_launch(void* ws, int B, int C, int H, int W, hipStream_t s);
 hipError_t zero_check_launch(const void* p, long long bytes, hipStream_t s);
+// warp.hip: zero `bytes` (a multiple of 4) at p as a kernel on the stream, never a memset node
+hipError_t zero_fill(void* p, size_t bytes, hipStream_t s);
 
+// occ.hip: the forward splat and the occlusion masks
 hipError_t splat_launch(const float* flow, long long flow_bstride, float* map, int B, int H, int W,
                         bool absolute, hipStream_t s);
 hipError_t occ_backward_launch(const float* flow, long long flow_bstride, float* occ, int B, int H,

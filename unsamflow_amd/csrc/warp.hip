@@ -26,6 +26,7 @@
 #include <climits>
 
 #include "interp_tap.h"
+#include "scatter_rows.h"
 #include "usf_common.h"
 #include "../../include/unsamflow_hip_hg.h"
 #include "../../include/unsamflow_hip_segpool.h"
@@ -33,30 +34,6 @@
 
 namespace usf {
 namespace {
-
-// Work split: a 256-thread workgroup covers PXB = 256/CS consecutive pixels x
-// CS channel slices (thread t: pixel t % PXB, channels t/PXB, t/PXB + CS, ...),
-// so consecutive lanes stay on consecutive pixels (coalesced flow/out/gout and
-// near-contiguous corner gathers / atomics) while small, channel-heavy pyramid
-// levels still spread over many workgroups instead of looping C channels per
-// lane.
-// (pixel block, sample) of this workgroup; with USF_WARP_CHUNK > 0 runs of
-// neighbouring pixel blocks (shared source rows / scatter targets) go to one XCD.
-// 16 blocks per chunk: warp forward L4 14.3 -> 12.6 us, L2 8.7 -> 7.9 us; the
-// backward and the splat are unchanged (profiles/ab_r01/warp_chunk_*.json)
-#ifndef USF_WARP_CHUNK
-#define USF_WARP_CHUNK 16
-#endif
-__device__ __forceinline__ void warp_block(int& bx, int& b) {
-  if (USF_WARP_CHUNK > 0) {
-    const int w = xcd_chunk(blockIdx.x + gridDim.x * blockIdx.y, gridDim.x * gridDim.y, USF_WARP_CHUNK);
-    bx = w % gridDim.x;
-    b = w / gridDim.x;
-  } else {
-    bx = blockIdx.x;
-    b = blockIdx.y;
-  }
-}
 
 #ifndef USF_WARP_FWD_PAIR
 #define USF_WARP_FWD_PAIR 1  // forward L4 23.9 -> 13.1 us, L2 11.8 -> 7.5 us (profiles/ab_r04/warp_corner_pairs.json)
@@ -162,71 +139,6 @@ __global__ __launch_bounds__(256) void warp_fwd_kernel(const float* __restrict__
   }
 }
 
-// grad_x scatter of one corner row (north: nw/ne, or south: sw/se) as a
-// wave-level reduce-by-key. Consecutive lanes are consecutive pixels, so along
-// a wave the target cells of a row are (nearly) monotone: lanes whose west
-// corner hits the same cell (the flow compresses, or floor() of a coordinate
-// that round-trips a hair below an integer) form a RUN, and a run's east cell
-// is usually the next run's west cell. Each run is summed onto its last lane
-// (log-step segmented scan over shuffles; the bound is the longest run in the
-// wave, channel-invariant, so the common no-collision case costs 2 shuffles),
-// the next run's head adds the previous run's east total into its west value,
-// and only run tails issue atomics: ~1 global atomic per cell and channel, and
-// no two lanes of one atomic instruction on the same address (those serialise).
-struct RowRuns {
-  int pos;      // lane's distance from its run head
-  int maxlen;   // longest run in the wave (wave-uniform)
-  bool tail;    // last lane of its run: issues the run's atomics
-  bool take;    // run head that adds the previous run's east total (cells chain)
-  bool give;    // run tail whose east total the next run's head takes
-};
-
-// key: row * (W + 1) + west column + 1, or a lane-unique negative value when the
-// row is outside the image (no atomics); has_left/has_right: the neighbour lane
-// exists and belongs to the same channel slice.
-__device__ __forceinline__ RowRuns row_runs(int key, bool m_w, bool m_e, bool has_left,
-                                            bool has_right) {
-  const int lane = threadIdx.x & 63;
-  const int kl = __shfl_up(key, 1);
-  const bool left_me = __shfl_up(m_e ? 1 : 0, 1) != 0;
-  const bool head = !(has_left && kl == key);
-  const unsigned long long heads = __ballot(head);
-  const unsigned long long upto = lane == 63 ? ~0ull : ((2ull << lane) - 1);
-  RowRuns r;
-  r.pos = lane - (63 - __clzll(heads & upto));
-  r.tail = lane == 63 || ((heads >> (lane + 1)) & 1ull) != 0;
-  int m = r.pos;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o));
-  r.maxlen = m + 1;
-  r.take = head && has_left && m_w && left_me && kl + 1 == key;
-  // every cross-lane read executes in all lanes (never behind a short-circuit:
-  // a ds_bpermute from an inactive lane returns garbage)
-  const bool right_takes = __shfl_down(r.take ? 1 : 0, 1) != 0;
-  r.give = r.tail && has_right && right_takes;
-  return r;
-}
-
-// segmented inclusive scan: lane l ends with the sum over [its run head, l]
-__device__ __forceinline__ float run_sum(float v, const RowRuns& r) {
-  for (int d = 1; d < r.maxlen; d <<= 1) {
-    const float u = __shfl_up(v, d);
-    if (r.pos >= d) v += u;
-  }
-  return v;
-}
-
-__device__ __forceinline__ void scatter_row(float* gc, int o_w, int o_e, bool m_w, bool m_e,
-                                            float vw, float ve, const RowRuns& r) {
-  const float se = run_sum(ve, r);
-  const float lt = __shfl_up(se, 1);
-  const float sw = run_sum(vw + (r.take ? lt : 0.f), r);
-  if (r.tail) {
-    if (m_w) atomicAdd(gc + o_w, sw);
-    if (m_e && !r.give) atomicAdd(gc + o_e, se);
-  }
-}
-
 // grad_x scatter over vertically adjacent PIXEL PAIRS: lane = (x, rows 2j and
 // 2j + 1). When both pixels hit the same west column and consecutive corner
 // rows (smooth flow), the first pixel's south row and the second's north row
@@ -234,11 +146,6 @@ __device__ __forceinline__ void scatter_row(float* gc, int o_w, int o_e, bool m_
 // reduce-by-key, so a pair scatters 3 corner rows instead of 4 (1.5 atomics per
 // pixel and channel instead of 2). Lanes whose pixels do not line up keep a
 // fourth row (issued only when some lane of the wave needs it).
-__device__ __forceinline__ int row_key(bool ok, int row, int xw, int H, int W, int lane) {
-  // keys alias nothing only for west columns in [-1, W-1]; elsewhere both cells are off-image
-  return ok && xw >= -1 && xw < W && (unsigned)row < (unsigned)H ? row * (W + 1) + xw + 1 : -(lane + 2);
-}
-
 template <bool BORDER, bool WANT_GF, int CS>
 __global__ __launch_bounds__(256) void warp_bwd_pair_kernel(const float* __restrict__ x,
                                                             const float* __restrict__ flow,
@@ -994,16 +901,7 @@ __global__ __launch_bounds__(256) void warp_gx_ovf_kernel(const float* __restric
     const bool any = tp.m_nw || tp.m_ne || tp.m_sw || tp.m_se;
     const int key = any ? (int)(((long long)b * (H + 1) + tp.yn + 1) * (W + 1) + tp.xw + 1) : -(lane + 2);
     const int kl = __shfl_up(key, 1);
-    const bool head = lane == 0 || kl != key;
-    const unsigned long long heads = __ballot(head);
-    const unsigned long long upto = lane == 63 ? ~0ull : ((2ull << lane) - 1);
-    RowRuns r;
-    r.pos = lane - (63 - __clzll(heads & upto));
-    r.tail = lane == 63 || ((heads >> (lane + 1)) & 1ull) != 0;
-    int m = r.pos;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o));
-    r.maxlen = m + 1;
+    const WaveRuns r = wave_runs(lane == 0 || kl != key);
     const float wv[4] = {tp.s * tp.e, tp.s * tp.w, tp.n * tp.e, tp.n * tp.w};
     const bool mk[4] = {tp.m_nw, tp.m_ne, tp.m_sw, tp.m_se};
     const int ok[4] = {tp.o_nw, tp.o_ne, tp.o_sw, tp.o_se};
@@ -1108,6 +1006,7 @@ __global__ __launch_bounds__(256) void zero_fill_kernel(unsigned* __restrict__ p
     }
   }
 }
+}  // namespace
 
 hipError_t zero_fill(void* p, size_t bytes, hipStream_t s) {
   const long long n = (long long)(bytes / 4);
@@ -1118,6 +1017,8 @@ hipError_t zero_fill(void* p, size_t bytes, hipStream_t s) {
                      head);
   return hipGetLastError();
 }
+
+namespace {
 
 struct BinLayout {
   long long novf_off, cnt_off, bins_off, wbin_off, ovf_off, total;
@@ -1405,185 +1306,12 @@ void bwd_launch_pad(const float* x, const float* flow, long long fbs, const floa
   }
 }
 
-// ----------------------------------------------------------- occlusion --
-// Forward bilinear splat of unit mass (warp_utils.py:26-94 get_corresponding_map,
-// used by get_occu_mask_backward :120-126): source pixel p of sample b lands at
-// (x, y) = (px + u, py + v) (ABS: (u, v) are absolute coordinates already) and
-// adds (1-|x-cx|)(1-|y-cy|) to each of its 4 integer neighbours (cx, cy) that
-// lies inside the image, with cx in {x0 = floor(x), x0 + 1}, computed in the
-// reference's fp32 order (contraction off). Same reduce-by-key scatter as the
-// warp's grad_x (lanes = consecutive source pixels): ~2 atomics per pixel.
-template <bool ABS>
-__global__ __launch_bounds__(256) void splat_kernel(const float* __restrict__ flow, long long fbs,
-                                                    float* __restrict__ map, int H, int W) {
-#pragma clang fp contract(off)
-  const int HW = H * W;
-  const int t = threadIdx.x;
-  const int lane = t & 63;
-  int bx, b;
-  warp_block(bx, b);
-  const int p = bx * 256 + t;
-  const bool valid = p < HW;
-  float x = 0.f, y = 0.f;
-  if (valid) {
-    const float* fb = flow + b * fbs;
-    const int py = p / W, px = p - py * W;
-    x = ABS ? fb[p] : (float)px + fb[p];
-    y = ABS ? fb[HW + p] : (float)py + fb[HW + p];
-  }
-  const float fx = floorf(x), fy = floorf(y);
-  const float fx1 = fx + 1.f, fy1 = fy + 1.f;
-  const float wm1 = (float)(W - 1), hm1 = (float)(H - 1);
-  // corner inside the image <=> clamp(c, 0, size-1) == c (the reference's test)
-  const bool vx0 = fx >= 0.f && fx <= wm1, vx1 = fx1 >= 0.f && fx1 <= wm1;
-  const bool vy0 = valid && fy >= 0.f && fy <= hm1, vy1 = valid && fy1 >= 0.f && fy1 <= hm1;
-  const float ax0 = 1.f - fabsf(x - fx), ax1 = 1.f - fabsf(x - fx1);
-  const float ay0 = 1.f - fabsf(y - fy), ay1 = 1.f - fabsf(y - fy1);
-  // integer corner indices, saturated so far-away targets cannot overflow
-  const int xi = fx < -1.f ? -2 : (fx > wm1 ? W : (int)fx);
-  const int yi = fy < -1.f ? -2 : (fy > hm1 ? H : (int)fy);
-  const bool kx = xi >= -1 && xi < W;  // keys alias nothing only for x0 in [-1, W-1]
-  const int kn = (vy0 && kx) ? yi * (W + 1) + xi + 1 : -(lane + 2);
-  const int ks = (vy1 && kx) ? (yi + 1) * (W + 1) + xi + 1 : -(lane + 2);
-  const bool has_left = lane != 0, has_right = lane != 63;
-  const bool m_nw = vx0 && vy0, m_ne = vx1 && vy0, m_sw = vx0 && vy1, m_se = vx1 && vy1;
-  const RowRuns rn = row_runs(kn, m_nw, m_ne, has_left, has_right);
-  const RowRuns rs = row_runs(ks, m_sw, m_se, has_left, has_right);
-  const int o_nw = m_nw || m_ne ? yi * W + xi : 0;
-  const int o_sw = m_sw || m_se ? (yi + 1) * W + xi : 0;
-  float* mb = map + (size_t)b * HW;
-  scatter_row(mb, o_nw, o_nw + 1, m_nw, m_ne, ax0 * ay0, ax1 * ay0, rn);
-  scatter_row(mb, o_sw, o_sw + 1, m_sw, m_se, ax0 * ay1, ax1 * ay1, rs);
-}
-
-// The splat over vertically adjacent pixel pairs (as warp_bwd_pair_kernel): a
-// lane owns rows 2j and 2j + 1 of one column; when both land on the same west
-// column and consecutive (unsaturated) corner rows, the shared row's four
-// weights are added in the lane and the pair scatters 3 rows instead of 4.
-struct SplatTap {
-  int xi, yi;
-  bool m_nw, m_ne, m_sw, m_se, kx, ky;  // ky: yi in [-1, H-1] (not saturated)
-  float ax0, ax1, ay0, ay1;
-};
-template <bool ABS>
-__device__ __forceinline__ SplatTap splat_tap(const float* __restrict__ fb, int p, int px, int py, bool valid,
-                                              int H, int W) {
-#pragma clang fp contract(off)
-  const int HW = H * W;
-  float x = 0.f, y = 0.f;
-  if (valid) {
-    x = ABS ? fb[p] : (float)px + fb[p];
-    y = ABS ? fb[HW + p] : (float)py + fb[HW + p];
-  }
-  SplatTap s;
-  const float fx = floorf(x), fy = floorf(y);
-  const float fx1 = fx + 1.f, fy1 = fy + 1.f;
-  const float wm1 = (float)(W - 1), hm1 = (float)(H - 1);
-  const bool vx0 = fx >= 0.f && fx <= wm1, vx1 = fx1 >= 0.f && fx1 <= wm1;
-  const bool vy0 = valid && fy >= 0.f && fy <= hm1, vy1 = valid && fy1 >= 0.f && fy1 <= hm1;
-  s.ax0 = 1.f - fabsf(x - fx);
-  s.ax1 = 1.f - fabsf(x - fx1);
-  s.ay0 = 1.f - fabsf(y - fy);
-  s.ay1 = 1.f - fabsf(y - fy1);
-  s.xi = fx < -1.f ? -2 : (fx > wm1 ? W : (int)fx);
-  s.yi = fy < -1.f ? -2 : (fy > hm1 ? H : (int)fy);
-  s.kx = s.xi >= -1 && s.xi < W;
-  s.ky = valid && s.yi >= -1 && s.yi < H;
-  s.m_nw = vx0 && vy0;
-  s.m_ne = vx1 && vy0;
-  s.m_sw = vx0 && vy1;
-  s.m_se = vx1 && vy1;
-  return s;
-}
-
-template <bool ABS>
-__global__ __launch_bounds__(256) void splat_pair_kernel(const float* __restrict__ flow, long long fbs,
-                                                         float* __restrict__ map, int H, int W) {
-#pragma clang fp contract(off)
-  const int HW = H * W, H2 = (H + 1) >> 1;
-  const int t = threadIdx.x;
-  const int lane = t & 63;
-  int bx, b;
-  warp_block(bx, b);
-  const int pp = bx * 256 + t;
-  const bool v0 = pp < W * H2;
-  const int px = v0 ? pp % W : 0, py = v0 ? 2 * (pp / W) : 0;
-  const bool v1 = v0 && py + 1 < H;
-  const float* fb = flow + b * fbs;
-  const int p0 = py * W + px;
-  const SplatTap s0 = splat_tap<ABS>(fb, p0, px, py, v0, H, W);
-  const SplatTap s1 = splat_tap<ABS>(fb, v1 ? p0 + W : p0, px, py + 1, v1, H, W);
-  const bool merged = v1 && s0.kx && s0.ky && s1.ky && s0.xi == s1.xi && s0.yi + 1 == s1.yi;
-  const bool split = __any(v1 && !merged);
-  const bool has_left = lane != 0, has_right = lane != 63;
-  auto key = [&](const SplatTap& s, int row, bool rowok) {
-    return rowok && s.kx ? row * (W + 1) + s.xi + 1 : -(lane + 2);
-  };
-  // rows: yi (north, valid iff its corners' row is in the image) and yi + 1
-  const RowRuns r0 = row_runs(key(s0, s0.yi, v0 && s0.yi >= 0 && s0.yi < H), s0.m_nw, s0.m_ne, has_left, has_right);
-  const RowRuns r1 = row_runs(key(s0, s0.yi + 1, v0 && s0.yi + 1 >= 0 && s0.yi + 1 < H), s0.m_sw, s0.m_se,
-                              has_left, has_right);
-  const RowRuns r2 = row_runs(key(s1, s1.yi + 1, v1 && s1.yi + 1 >= 0 && s1.yi + 1 < H), s1.m_sw, s1.m_se,
-                              has_left, has_right);
-  const bool own1 = v1 && !merged;
-  RowRuns r3{};
-  if (split)
-    r3 = row_runs(key(s1, s1.yi, own1 && s1.yi >= 0 && s1.yi < H), s1.m_nw && own1, s1.m_ne && own1,
-                  has_left, has_right);
-  float* mb = map + (size_t)b * HW;
-  const int o0 = s0.yi * W + s0.xi, o1 = s1.yi * W + s1.xi;
-  const int on0 = s0.m_nw || s0.m_ne ? o0 : 0, os0 = s0.m_sw || s0.m_se ? o0 + W : 0;
-  const int on1 = s1.m_nw || s1.m_ne ? o1 : 0, os1 = s1.m_sw || s1.m_se ? o1 + W : 0;
-  scatter_row(mb, on0, on0 + 1, s0.m_nw, s0.m_ne, s0.ax0 * s0.ay0, s0.ax1 * s0.ay0, r0);
-  const float vw = merged ? s0.ax0 * s0.ay1 + s1.ax0 * s1.ay0 : s0.ax0 * s0.ay1;
-  const float ve = merged ? s0.ax1 * s0.ay1 + s1.ax1 * s1.ay0 : s0.ax1 * s0.ay1;
-  scatter_row(mb, os0, os0 + 1, s0.m_sw, s0.m_se, vw, ve, r1);
-  scatter_row(mb, os1, os1 + 1, s1.m_sw, s1.m_se, s1.ax0 * s1.ay1, s1.ax1 * s1.ay1, r2);
-  if (split) scatter_row(mb, on1, on1 + 1, s1.m_nw && own1, s1.m_ne && own1, s1.ax0 * s1.ay0, s1.ax1 * s1.ay0, r3);
-}
-
-// occ = clamp(map, 0, 1) < th ? 1 : 0 (get_occu_mask_backward :124-126); in
-// place (occ == map), or (REZERO) from a persistent map that is zeroed as read
-template <bool REZERO>
-__global__ __launch_bounds__(256) void occ_threshold_kernel(float* m, float* occ, long long n, float th) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const float v = m[i];
-  if (REZERO) m[i] = 0.f;
-  occ[i] = fminf(fmaxf(v, 0.f), 1.f) < th ? 1.f : 0.f;
-}
-
-// Both directions of a with_bk loss at once (usf_occ_vis_pair_persist_f32):
-// the splat map is interleaved [B][2][H][W] (half j = 0: the splat of
-// flow12 = top[:, :2], j = 1: of flow21 = top[:, 2:]), and the threshold pass
-// writes the visibility masks the loss uses, 1 - occ, direction-major:
-// vis[0][b] = 1 - occ(flow21) (flow_loss.py:102 vis_mask1), vis[1][b] =
-// 1 - occ(flow12) (:103 vis_mask2), each a contiguous [B,1,H,W]; the map is
-// re-zeroed as read (its only reader).
-__global__ __launch_bounds__(256) void occ_vis_pair_kernel(float* __restrict__ m, float* __restrict__ vis, int HW,
-                                                           int B, float th) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long n = 2LL * B * HW;
-  if (i >= n) return;
-  const int b2 = (int)(i / HW), p = (int)(i - (long long)b2 * HW);
-  const int b = b2 >> 1, j = b2 & 1;
-  const float v = m[i];
-  m[i] = 0.f;
-  const float occ = fminf(fmaxf(v, 0.f), 1.f) < th ? 1.f : 0.f;
-  vis[((long long)(1 - j) * B + b) * HW + p] = 1.f - occ;
-}
-
 }  // namespace
 
 int device_errors(hipStream_t s, bool clear, int mask) {
-  int v = 0;
   if (hipStreamSynchronize(s) != hipSuccess) return -1;
-  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_dev_errors), sizeof(int)) != hipSuccess) return -1;
-  if (clear && (v & mask) != 0) {
-    const int z = v & ~mask;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_dev_errors), &z, sizeof(int)) != hipSuccess) return -1;
-  }
-  v &= mask;
+  const int v = read_clear_flags(HIP_SYMBOL(g_dev_errors), clear, mask);
+  if (v < 0) return -1;
   // segpool.hip and hg.hip keep their own flag words (one code object per source file)
   const int sp = (mask & USF_DEVERR_SEGPOOL_BAD_ID) ? segpool_device_errors(clear) : 0;
   const int hg = (mask & USF_DEVERR_HG_BAD_ID) ? hg_device_errors(clear) : 0;
@@ -1675,115 +1403,5 @@ hipError_t warp_persist_check_launch(void* ws, int B, int C, int H, int W, hipSt
 
 long long warp_bwd_workspace(int B, int H, int W) { return bin_layout(B, H, W).total; }
 long long warp_bwd_persist_workspace(int B, int C, int H, int W) { return bin_layout2(B, C, H, W).total; }
-
-hipError_t splat_launch(const float* flow, long long fbs, float* map, int B, int H, int W,
-                        bool absolute, hipStream_t s) {
-  hipError_t e = zero_fill(map, (size_t)B * H * W * sizeof(float), s);
-  if (e != hipSuccess) return e;
-  return splat_scatter(flow, fbs, map, B, H, W, absolute, s);
-}
-
-// the splat's scatter into a map that is already zero
-hipError_t splat_scatter(const float* flow, long long fbs, float* map, int B, int H, int W, bool absolute,
-                         hipStream_t s) {
-  const long pairs = (long)W * ((H + 1) / 2);
-  if (pairs >= 4096 && variant_override(2) != 0) {  // pixel pairs (as the warp backward)
-    const dim3 grid((unsigned)((pairs + 255) / 256), (unsigned)B);
-    if (absolute)
-      hipLaunchKernelGGL((splat_pair_kernel<true>), grid, dim3(256), 0, s, flow, fbs, map, H, W);
-    else
-      hipLaunchKernelGGL((splat_pair_kernel<false>), grid, dim3(256), 0, s, flow, fbs, map, H, W);
-    return hipGetLastError();
-  }
-  const dim3 grid((unsigned)((H * W + 255) / 256), (unsigned)B);
-  if (absolute)
-    hipLaunchKernelGGL((splat_kernel<true>), grid, dim3(256), 0, s, flow, fbs, map, H, W);
-  else
-    hipLaunchKernelGGL((splat_kernel<false>), grid, dim3(256), 0, s, flow, fbs, map, H, W);
-  return hipGetLastError();
-}
-
-hipError_t occ_backward_persist_launch(const float* flow, long long fbs, float* occ, float* map, int B, int H,
-                                       int W, float th, hipStream_t s) {
-  // map: the caller's persistent splat buffer, zero on entry; the threshold pass
-  // is its only reader and leaves it zero again (no fill launch)
-  hipError_t e = splat_scatter(flow, fbs, map, B, H, W, false, s);
-  if (e != hipSuccess) return e;
-  const long long n = (long long)B * H * W;
-  hipLaunchKernelGGL(occ_threshold_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, map, occ, n,
-                     th);
-  return hipGetLastError();
-}
-
-hipError_t occ_vis_pair_persist_launch(const float* flow4, float* vis, float* map, int B, int H, int W, float th,
-                                      hipStream_t s) {
-  // a dense [B,4,H,W] flow is a [2B,2,H,W] batch of (flow12, flow21) pairs: one
-  // splat launch over 2B samples fills the interleaved map
-  const long long HW = (long long)H * W;
-  hipError_t e = splat_scatter(flow4, 2 * HW, map, 2 * B, H, W, false, s);
-  if (e != hipSuccess) return e;
-  const long long n = 2LL * B * HW;
-  hipLaunchKernelGGL(occ_vis_pair_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, map, vis, (int)HW, B,
-                     th);
-  return hipGetLastError();
-}
-
-hipError_t occ_backward_launch(const float* flow, long long fbs, float* occ, int B, int H, int W,
-                               float th, hipStream_t s) {
-  hipError_t e = splat_launch(flow, fbs, occ, B, H, W, false, s);
-  if (e != hipSuccess) return e;
-  const long long n = (long long)B * H * W;
-  hipLaunchKernelGGL(occ_threshold_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, occ, occ, n,
-                     th);
-  return hipGetLastError();
-}
-
-namespace {
-// Forward-backward consistency occlusion (get_occu_mask_bidirection,
-// warp_utils.py:109-117), one thread per pixel:
-//   w21  = flow_warp(flow21, flow12, pad="zeros")            (:110)
-//   diff = flow12 + w21                                        (:111)
-//   mag  = (f12_u^2 + f12_v^2) + (w21_u^2 + w21_v^2)           (:112-114)
-//   occ  = (diff_u^2 + diff_v^2) > 0.01 * mag + 0.5 ? 1 : 0    (:115-117)
-// Each product and sum is rounded separately, as torch evaluates them (the
-// channel sums over 2 elements are a + b), so the mask decision is the
-// reference's bit for bit where the warp is.
-__global__ __launch_bounds__(256) void occ_bidir_kernel(const float* __restrict__ f12, long long bs12,
-                                                        const float* __restrict__ f21, long long bs21,
-                                                        float* __restrict__ occ, int H, int W,
-                                                        float scale, float bias) {
-#pragma clang fp contract(off)
-  const int HW = H * W;
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  const int b = blockIdx.y;
-  if (p >= HW) return;
-  const int y = p / W, x = p - y * W;
-  const float* a = f12 + b * bs12;
-  const float* c = f21 + b * bs21;
-  const float u = a[p], v = a[HW + p];
-  const Tap t = make_tap(u, v, x, y, H, W, false);
-  const float wnw = t.s * t.e, wne = t.s * t.w, wsw = t.n * t.e, wse = t.n * t.w;
-  float w[2];
-#pragma unroll
-  for (int ch = 0; ch < 2; ++ch) {
-    const float* cc = c + ch * HW;
-    const float vnw = t.m_nw ? cc[t.o_nw] : 0.f, vne = t.m_ne ? cc[t.o_ne] : 0.f;
-    const float vsw = t.m_sw ? cc[t.o_sw] : 0.f, vse = t.m_se ? cc[t.o_se] : 0.f;
-    w[ch] = vnw * wnw + vne * wne + vsw * wsw + vse * wse;
-  }
-  const float du = u + w[0], dv = v + w[1];
-  const float mag = (u * u + v * v) + (w[0] * w[0] + w[1] * w[1]);
-  const float th = scale * mag + bias;
-  occ[(size_t)b * HW + p] = (du * du + dv * dv) > th ? 1.f : 0.f;
-}
-}  // namespace
-
-hipError_t occ_bidirection_launch(const float* flow12, long long bs12, const float* flow21, long long bs21,
-                                  float* occ, int B, int H, int W, float scale, float bias, hipStream_t s) {
-  const int HW = H * W;
-  hipLaunchKernelGGL(occ_bidir_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)B), dim3(256), 0, s,
-                     flow12, bs12, flow21, bs21, occ, H, W, scale, bias);
-  return hipGetLastError();
-}
 
 }  // namespace usf
