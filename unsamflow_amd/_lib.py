@@ -249,6 +249,22 @@ HG_SYMBOLS = {
     ),
 }
 
+# the conv epilogues (include/unsamflow_hip_convepi.h), versioned the same way
+CONVEPI_API_VERSION = 1
+CONVEPI_TILE_SLOTS = 1024
+CONVEPI_CHAIN = 64
+CONVEPI_TARGET_WGS = 16384
+CONVEPI_SYMBOLS = {
+    "usf_convepi_api_version": ([], ctypes.c_int),
+    "usf_convepi_fwd_f32": ([_c_float_p] * 2 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_void_p], ctypes.c_int),
+    "usf_convepi_bwd_workspace": ([ctypes.c_int] * 4, ctypes.c_longlong),
+    "usf_convepi_bwd_f32": (
+        [_c_float_p, ctypes.c_longlong] + [_c_float_p] * 4 + [ctypes.c_longlong] + [ctypes.c_int] * 4
+        + [ctypes.c_float, ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+}
+
 _lock = threading.Lock()
 _lib = None
 _load_error: str | None = None
@@ -274,7 +290,7 @@ def load() -> ctypes.CDLL:
             raise RuntimeError(_load_error)
         lib = ctypes.CDLL(str(_LIB_PATH), mode=ctypes.RTLD_LOCAL)
         for name, (argtypes, restype) in {**_SIGNATURES, **CENSUS_SYMBOLS, **AR_SYMBOLS, **SEGPOOL_SYMBOLS,
-                                          **HG_SYMBOLS}.items():
+                                          **HG_SYMBOLS, **CONVEPI_SYMBOLS}.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = restype
@@ -293,6 +309,9 @@ def load() -> ctypes.CDLL:
         v = lib.usf_hg_api_version()
         if v != HG_API_VERSION:
             raise RuntimeError(f"libunsamflow_hip.so hg API version {v} != expected {HG_API_VERSION}")
+        v = lib.usf_convepi_api_version()
+        if v != CONVEPI_API_VERSION:
+            raise RuntimeError(f"libunsamflow_hip.so convepi API version {v} != expected {CONVEPI_API_VERSION}")
         _lib = lib
         return lib
 

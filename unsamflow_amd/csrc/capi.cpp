@@ -12,6 +12,7 @@
 #include "../../include/unsamflow_hip.h"
 #include "../../include/unsamflow_hip_ar.h"
 #include "../../include/unsamflow_hip_census.h"
+#include "../../include/unsamflow_hip_convepi.h"
 #include "../../include/unsamflow_hip_hg.h"
 #include "../../include/unsamflow_hip_segpool.h"
 #include "usf_common.h"
@@ -1224,6 +1225,76 @@ int usf_area_pyramid_f32(const float* x, float* out1, float* out2, float* out3, 
   }
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn, area_pyramid_launch(x, out1, out2, out3, (long long)B * C, H, W, (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+// ------------------------------------------------ unsamflow_hip_convepi.h --
+int usf_convepi_api_version(void) { return USF_CONVEPI_API_VERSION; }
+
+static bool check_convepi(const char* fn, int B, int C, int H, int W, float slope) {
+  if (!check_dims(fn, B, C, H, W)) return false;
+  if (!(slope > 0.f)) {  // the sign of y is the sign of the pre-activation only then
+    set_error("%s: slope=%g (must be > 0)", fn, (double)slope);
+    return false;
+  }
+  return true;
+}
+
+int usf_convepi_fwd_f32(float* y, const float* bias, int B, int C, int H, int W, float slope, void* stream) {
+  clear_error();
+  const char* fn = "usf_convepi_fwd_f32";
+  if (!check_convepi(fn, B, C, H, W, slope)) return USF_EINVAL;
+  if (!y || !bias) {
+    set_error("%s: null pointer", fn);
+    return USF_EINVAL;
+  }
+  if ((uintptr_t)y % 16 != 0 || (uintptr_t)bias % 4 != 0) {
+    set_error("%s: y must be 16-byte and bias 4-byte aligned", fn);
+    return USF_EINVAL;
+  }
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn, convepi_fwd_launch(y, bias, B, C, H, W, slope, (hipStream_t)stream), (hipStream_t)stream);
+}
+
+long long usf_convepi_bwd_workspace(int B, int C, int H, int W) {
+  return (B > 0 && C > 0 && H > 0 && W > 0) ? convepi_bwd_workspace(B, C, H, W) : -1;
+}
+
+int usf_convepi_bwd_f32(const float* grad_out, long long gout_bstride, const float* y, float* grad_in,
+                        float* grad_bias, float* workspace, long long workspace_floats, int B, int C, int H, int W,
+                        float slope, void* stream) {
+  clear_error();
+  const char* fn = "usf_convepi_bwd_f32";
+  if (!check_convepi(fn, B, C, H, W, slope)) return USF_EINVAL;
+  const long long need = convepi_bwd_workspace(B, C, H, W);
+  if (need < 0) {
+    set_error("%s: shape B=%d C=%d H=%d W=%d too large for the bias-gradient split", fn, B, C, H, W);
+    return USF_EINVAL;
+  }
+  const bool act = slope != 1.f;
+  if (!grad_out || (uintptr_t)grad_out % 4 != 0 || gout_bstride < (long long)C * H * W) {
+    set_error("%s: grad_out null or misaligned, or gout_bstride=%lld < C*H*W", fn, gout_bstride);
+    return USF_EINVAL;
+  }
+  if (act ? (!y || !grad_in || (uintptr_t)y % 16 != 0 || (uintptr_t)grad_in % 16 != 0) : (y || grad_in)) {
+    set_error("%s: y and grad_in must be 16-byte aligned tensors with an activation, NULL without (slope=%g)", fn,
+              (double)slope);
+    return USF_EINVAL;
+  }
+  if (!grad_bias && !act) {
+    set_error("%s: nothing to compute (no activation and no grad_bias)", fn);
+    return USF_EINVAL;
+  }
+  if (grad_bias && ((uintptr_t)grad_bias % 4 != 0 ||
+                    (need > 0 && (!workspace || workspace_floats < need || (uintptr_t)workspace % 4 != 0)))) {
+    set_error("%s: grad_bias misaligned, or workspace of %lld floats null, misaligned or short (%lld given)", fn,
+              need, workspace_floats);
+    return USF_EINVAL;
+  }
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn,
+                convepi_bwd_launch(grad_out, gout_bstride, y, grad_in, grad_bias, workspace, B, C, H, W, slope,
+                                   (hipStream_t)stream),
                 (hipStream_t)stream);
 }
 

@@ -214,6 +214,12 @@ hipError_t hg_loss_fwd_launch(const float* flow, long long fbs, const float* seg
 hipError_t hg_loss_bwd_launch(const float* flow, long long fbs, const float* seg, const int* records,
                               const float* gloss, float* gflow, int B, int H, int W, hipStream_t s);
 
+// convepi.hip: the conv epilogues (bias + LeakyReLU in place; their backward with the bias gradient)
+long long convepi_bwd_workspace(int B, int C, int H, int W);  // floats; -1: shape not taken
+hipError_t convepi_fwd_launch(float* y, const float* bias, int B, int C, int H, int W, float slope, hipStream_t s);
+hipError_t convepi_bwd_launch(const float* gout, long long gbs, const float* y, float* gin, float* gbias,
+                              float* workspace, int B, int C, int H, int W, float slope, hipStream_t s);
+
 hipError_t upsample_fwd_launch(const float* x, float* out, int B, int C, int H, int W, int k,
                                hipStream_t s);
 hipError_t upsample_bwd_launch(const float* gout, float* gx, int B, int C, int H, int W, int k,

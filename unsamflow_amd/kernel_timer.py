@@ -169,6 +169,15 @@ def site_launcher(op: str, key, device, seed: int = 0):
         cat = torch.empty(B, 81 + C + 2, H, W, device=device)
         mask = ops.corr_act_mask(B, H, W, 4, device, C=C)
         return lambda: ops.corr_forward_ex(x1, x2, 4, cat[:, :81], 0.1, act_mask=mask)
+    if op in ("conv_epi_fwd", "conv_epi_bwd"):  # a conv_block's bias + LeakyReLU pass and its backward
+        B, C, H, W, act = key[:5]
+        slope = 0.1 if act else 1.0
+        bias = torch.randn(C, device=device, generator=g)
+        y = torch.randn(B, C, H, W, device=device, generator=g)
+        if op == "conv_epi_fwd":  # in place, again and again: the values drift, the traffic does not
+            return lambda: ops.conv_epilogue_forward(y, bias, slope)
+        go = torch.randn(B, C, H, W, device=device, generator=g)
+        return lambda: ops.conv_epilogue_backward(go, y if act else None, slope)
     if op in ("corr_fwd", "corr_bwd"):
         B, C, H, W = key[:4]
         x1 = torch.randn(B, C, H, W, device=device, generator=g)

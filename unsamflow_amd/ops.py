@@ -1340,3 +1340,92 @@ def area_pyramid(x: torch.Tensor):
         rc = lib.usf_area_pyramid_f32(*_args)
     _lib.check(rc, "usf_area_pyramid_f32")
     return outs
+
+
+def _conv_epi_args(y, bias, slope):
+    _require_device_f32("y", y)
+    _require_device_f32("bias", bias)
+    B, C, H, W = _nchw("y", y)
+    if not y.is_contiguous():
+        raise ValueError(f"y must be dense NCHW (strides {y.stride()})")
+    if tuple(bias.shape) != (C,) or bias.device != y.device:
+        raise ValueError(f"bias must be [{C}] on {y.device}, got {tuple(bias.shape)} on {bias.device}")
+    slope = float(slope)
+    if not slope > 0.0:
+        raise ValueError(f"slope={slope} must be > 0 (1 = no activation)")
+    return B, C, H, W, slope
+
+
+def conv_epilogue_forward(raw: torch.Tensor, bias: torch.Tensor, slope: float = 1.0) -> torch.Tensor:
+    """In place on ``raw`` [B,C,H,W] (a bias-free convolution's output):
+    ``raw = leaky_relu(raw + bias[c], slope)``, bit-identical to ``add_`` then
+    ``leaky_relu_``; ``slope == 1`` is the bias add alone. Returns ``raw``."""
+    B, C, H, W, slope = _conv_epi_args(raw, bias, slope)
+    if raw.numel() == 0:
+        return raw
+    dev = raw.device
+    lib = _lib.load()
+    _args = (raw.data_ptr(), bias.contiguous().data_ptr(), B, C, H, W, slope, _lib.stream_handle(dev),)
+    # algorithmic bytes: raw read and written, bias read
+    with torch.cuda.device(dev), _kt.timed("conv_epi_fwd", (B, C, H, W, slope != 1.0), dev,
+                                           8 * B * C * H * W + 4 * C):
+        rc = lib.usf_convepi_fwd_f32(*_args)
+    _lib.check(rc, "usf_convepi_fwd_f32")
+    return raw
+
+
+def conv_epilogue_backward(grad_out: torch.Tensor, y: torch.Tensor | None, slope: float,
+                           need_bias: bool = True) -> tuple[torch.Tensor, torch.Tensor | None]:
+    """The backward of :func:`conv_epilogue_forward` -> ``(grad_in, grad_bias)``.
+
+    With an activation (``slope != 1``; ``y`` is the forward's result)
+    ``grad_in = leaky_relu_backward(grad_out, y, slope)`` (bit-identical), dense;
+    without one ``y`` is None and ``grad_in`` is ``grad_out`` itself.
+    ``grad_bias[c]`` is the sum of ``grad_in`` over (b, h, w), from the same pass
+    and deterministic; ``need_bias=False`` returns None and requests no workspace.
+    ``grad_out`` may be a channel slice of an NCHW-contiguous tensor (a concat's
+    gradient): it is read in place, no dense copy."""
+    _require_device_f32("grad_out", grad_out)
+    B, C, H, W = _nchw("grad_out", grad_out)
+    slope = float(slope)
+    if not slope > 0.0:
+        raise ValueError(f"slope={slope} must be > 0 (1 = no activation)")
+    act = slope != 1.0
+    dev = grad_out.device
+    if act:
+        if y is None:
+            raise ValueError("y (the forward's result) is needed with an activation")
+        _require_device_f32("y", y)
+        if tuple(y.shape) != (B, C, H, W) or y.device != dev or not y.is_contiguous():
+            raise ValueError(f"y must be a dense {(B, C, H, W)} tensor on {dev}")
+    elif y is not None:
+        raise ValueError("y must be None without an activation (slope == 1)")
+    if not act and not need_bias:
+        return grad_out, None
+    if grad_out.numel() == 0:
+        return (torch.empty_like(y) if act else grad_out), (grad_out.new_zeros(C) if need_bias else None)
+    try:
+        gbs = _plane_slice_stride("grad_out", grad_out, (B, C, H, W))
+        g = grad_out
+    except ValueError:  # any other layout: one dense copy, as the convolution would make
+        g = grad_out.contiguous()
+        gbs = C * H * W
+    lib = _lib.load()
+    gin = torch.empty((B, C, H, W), device=dev, dtype=torch.float32) if act else None
+    gbias = ws = None
+    nws = 0
+    if need_bias:
+        nws = int(lib.usf_convepi_bwd_workspace(B, C, H, W))
+        if nws < 0:
+            raise ValueError(f"conv_epilogue_backward: shape {(B, C, H, W)} is too large for the bias-gradient split")
+        gbias = torch.empty(C, device=dev, dtype=torch.float32)
+        if nws:
+            ws = torch.empty(nws, device=dev, dtype=torch.float32)
+    _args = (g.data_ptr(), gbs, _ptr(y), _ptr(gin), _ptr(gbias), _ptr(ws), nws, B, C, H, W, slope,
+             _lib.stream_handle(dev),)
+    # algorithmic bytes: grad_out (and y) read, grad_in written with an activation; grad_bias written
+    with torch.cuda.device(dev), _kt.timed("conv_epi_bwd", (B, C, H, W, act), dev,
+                                           (12 if act else 4) * B * C * H * W + 4 * C):
+        rc = lib.usf_convepi_bwd_f32(*_args)
+    _lib.check(rc, "usf_convepi_bwd_f32")
+    return (gin if act else grad_out), gbias

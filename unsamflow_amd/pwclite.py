@@ -27,12 +27,43 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 
+def _channels_last(t: torch.Tensor) -> bool:
+    return t.dim() == 4 and not t.is_contiguous() and t.is_contiguous(memory_format=torch.channels_last)
+
+
+class ConvBlock(nn.Sequential):
+    """``Sequential(Conv2d[, LeakyReLU])`` whose bias add and activation run as
+    one in-place HIP pass after the bias-free convolution (conv_epilogue.py)
+    where that applies: FUSED_CONV_EPILOGUE, ``self.fused`` (PWCLite clears it
+    when its ops are injected), fp32 dense NCHW on a ROCm device, a positive
+    slope. Everywhere else it is the Sequential: the same numbers either way
+    (the bias gradient's summation order aside)."""
+
+    fused = True
+
+    def forward(self, x):
+        conv = self[0]
+        slope = self[1].negative_slope if len(self) > 1 else 1.0
+        if not (FUSED_CONV_EPILOGUE and self.fused and x.is_cuda and x.dtype == torch.float32
+                and conv.weight.dtype == torch.float32 and conv.bias is not None and slope > 0
+                and not _channels_last(x) and not _channels_last(conv.weight)
+                and not torch.is_autocast_enabled()):
+            return super().forward(x)
+        from .conv_epilogue import bias_act_
+
+        raw = conv._conv_forward(x, conv.weight, None)
+        if not raw.is_contiguous():  # a layout of MIOpen's choosing (channels-last weights): the composition
+            raw = raw + conv.bias.view(1, -1, 1, 1)
+            return self[1](raw) if len(self) > 1 else raw
+        return bias_act_(raw, conv.bias, slope)
+
+
 def conv_block(cin: int, cout: int, k: int = 3, stride: int = 1, dilation: int = 1, relu: bool = True) -> nn.Sequential:
     """Conv2d ('same' padding for odd k) [+ LeakyReLU(0.1, inplace)] — key layout ``.0.weight``."""
     layers = [nn.Conv2d(cin, cout, k, stride=stride, dilation=dilation, padding=((k - 1) * dilation) // 2, bias=True)]
     if relu:
         layers.append(nn.LeakyReLU(0.1, inplace=True))
-    return nn.Sequential(*layers)
+    return ConvBlock(*layers)
 
 
 def full_segs_to_adj_maps(full_segs: torch.Tensor, win_size: int = 9, pad_mode: str = "replicate") -> torch.Tensor:
@@ -159,6 +190,9 @@ def _default_corr():
 
 # the decoder's x2 flow upsampling and warp of x2 as one launch (upsample.upsample_warp)
 FUSED_UP_WARP = True
+# every conv_block's bias add and LeakyReLU as one in-place pass after the bias-free
+# convolution, and their backward with the bias gradient (conv_epilogue.bias_act_)
+FUSED_CONV_EPILOGUE = True
 # the mask-feature branch's per-segment max pool and spread as HIP kernels
 # (segpool.segment_max_spread) instead of the one-hot composition (the same numbers)
 FUSED_SEG_POOL = True
@@ -214,6 +248,10 @@ class PWCLite(nn.Module):
                 self.mask_aggregation = conv_block(32, 32, k=1)
             elif cfg.aggregation_type == "concat":
                 self.mask_aggregation = conv_block(64, 32, k=1)
+        if not self.fused_corr_cat:  # injected ops: the reference composition throughout
+            for m in self.modules():
+                if isinstance(m, ConvBlock):
+                    m.fused = False
 
     def num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
