@@ -265,6 +265,25 @@ CONVEPI_SYMBOLS = {
     ),
 }
 
+# the key-object augmentation (include/unsamflow_hip_fakeobj.h), versioned the same way
+FAKEOBJ_API_VERSION = 1
+FAKEOBJ_MAX_K = 8
+DEVERR_FAKEOBJ_BAD_SLOT = 16
+FAKEOBJ_SYMBOLS = {
+    "usf_fakeobj_api_version": ([], ctypes.c_int),
+    "usf_fakeobj_paste_crop_f32": (
+        [_c_float_p] * 3 + [ctypes.c_longlong] + [_c_float_p] * 4 + [ctypes.c_void_p] + [_c_float_p] * 4
+        + [ctypes.c_int] * 9 + [ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+    "usf_fakeobj_push_partials": ([ctypes.c_int] * 3, ctypes.c_int),
+    "usf_fakeobj_push_f32": (
+        [_c_float_p] * 3 + [ctypes.c_longlong, ctypes.c_void_p] + [_c_float_p] * 4 + [ctypes.c_int] * 4
+        + [ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+}
+
 _lock = threading.Lock()
 _lib = None
 _load_error: str | None = None
@@ -290,7 +309,7 @@ def load() -> ctypes.CDLL:
             raise RuntimeError(_load_error)
         lib = ctypes.CDLL(str(_LIB_PATH), mode=ctypes.RTLD_LOCAL)
         for name, (argtypes, restype) in {**_SIGNATURES, **CENSUS_SYMBOLS, **AR_SYMBOLS, **SEGPOOL_SYMBOLS,
-                                          **HG_SYMBOLS, **CONVEPI_SYMBOLS}.items():
+                                          **HG_SYMBOLS, **CONVEPI_SYMBOLS, **FAKEOBJ_SYMBOLS}.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = restype
@@ -312,6 +331,9 @@ def load() -> ctypes.CDLL:
         v = lib.usf_convepi_api_version()
         if v != CONVEPI_API_VERSION:
             raise RuntimeError(f"libunsamflow_hip.so convepi API version {v} != expected {CONVEPI_API_VERSION}")
+        v = lib.usf_fakeobj_api_version()
+        if v != FAKEOBJ_API_VERSION:
+            raise RuntimeError(f"libunsamflow_hip.so fake-object API version {v} != expected {FAKEOBJ_API_VERSION}")
         _lib = lib
         return lib
 

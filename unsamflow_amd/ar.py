@@ -301,6 +301,18 @@ def ar_loss(pred, target, noc, eps: float = 0.0, q: float = 1.0, denom=None, fus
     return ARLossFunction.apply(pred, target, noc, float(eps), float(q), denom)
 
 
+def crop_offsets(h: int, w: int, crop_sz, generator=None) -> tuple[int, int]:
+    """(y1, x1) of oc_transforms.random_crop's window: x is drawn first, then y,
+    each from ``randint(0, size - crop)``; a dimension equal to the crop draws
+    nothing and gives 0."""
+    c_h, c_w = crop_sz
+    if c_h > h or c_w > w:
+        raise ValueError(f"crop {(c_h, c_w)} larger than the image {(h, w)}")
+    x1 = int(torch.randint(0, w - c_w, (), generator=generator)) if w > c_w else 0
+    y1 = int(torch.randint(0, h - c_h, (), generator=generator)) if h > c_h else 0
+    return y1, x1
+
+
 def random_crop(imgs, flow, noc, crop_sz, generator=None):
     """oc_transforms.random_crop as the trainers call it (three tensors): one
     random window of ``crop_sz`` = (h, w) as views of all three. The offsets (x
@@ -308,11 +320,8 @@ def random_crop(imgs, flow, noc, crop_sz, generator=None):
     dimension equal to the crop gives offset 0."""
     h, w = imgs.shape[-2:]
     c_h, c_w = crop_sz
-    if c_h > h or c_w > w:
-        raise ValueError(f"crop {(c_h, c_w)} larger than the image {(h, w)}")
+    y1, x1 = crop_offsets(h, w, crop_sz, generator)
     if c_h == h and c_w == w:
         return imgs, flow, noc
-    x1 = int(torch.randint(0, w - c_w, (), generator=generator)) if w > c_w else 0
-    y1 = int(torch.randint(0, h - c_h, (), generator=generator)) if h > c_h else 0
     win = (slice(None), slice(None), slice(y1, y1 + c_h), slice(x1, x1 + c_w))
     return imgs[win], flow[win], noc[win]

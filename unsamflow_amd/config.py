@@ -21,8 +21,13 @@ reference's JSON configs:
   configs/sintel_aug+hg.json applied (from epoch 150): the homography
   smoothness loss (``smooth_type "homography"``, ``w_sm 0.1``, KITTI
   ``ransac_threshold 0.5``; Sintel leaves it to unFlowLoss's default of 3) and
-  ``w_ar 0.1``. ``key_obj_aug`` stays ``False``: fake-object insertion is not
-  built (unsamflow_amd.homography, flow_loss.unFlowLoss)
+  ``w_ar 0.1``; ``key_obj_aug`` stays ``False`` here (unsamflow_amd.homography,
+  flow_loss.unFlowLoss)
+* ``kitti_aug()`` / ``sintel_aug()`` and ``kitti_aug_hg()`` / ``sintel_aug_hg()``
+  — the stage-1 AR config and the stage-2 homography config with the rest of
+  ``train.stage2`` of configs/*_aug.json / configs/*_aug+hg.json applied:
+  ``key_obj_aug true``, ``key_obj_count 3``, ``w_ar 0.1`` (from epoch 150: the
+  key-object augmentation of the third pass, unsamflow_amd.fake_object)
 
 ``load_json`` reads a reference-format JSON file with the one-level
 ``base_configs`` inheritance + recursive merge of utils/config_parser.py:11-33.
@@ -191,4 +196,32 @@ def sintel_stage2_hg() -> AttrDict:
     cfg = sintel_stage1_ar()
     cfg.loss.update(_STAGE2_HG_LOSS)
     cfg.train.w_ar = 0.1
+    return cfg
+
+
+# the key-object part of train.stage2 of configs/*_aug.json and configs/*_aug+hg.json
+_KEY_OBJ_TRAIN = {"key_obj_aug": True, "key_obj_count": 3, "w_ar": 0.1}
+
+
+def kitti_aug() -> AttrDict:
+    cfg = kitti_stage1_ar()
+    cfg.train.update(_KEY_OBJ_TRAIN)
+    return cfg
+
+
+def sintel_aug() -> AttrDict:
+    cfg = sintel_stage1_ar()
+    cfg.train.update(_KEY_OBJ_TRAIN)
+    return cfg
+
+
+def kitti_aug_hg() -> AttrDict:
+    cfg = kitti_stage2_hg()
+    cfg.train.update(_KEY_OBJ_TRAIN)
+    return cfg
+
+
+def sintel_aug_hg() -> AttrDict:
+    cfg = sintel_stage2_hg()
+    cfg.train.update(_KEY_OBJ_TRAIN)
     return cfg

@@ -13,6 +13,7 @@
 #include "../../include/unsamflow_hip_ar.h"
 #include "../../include/unsamflow_hip_census.h"
 #include "../../include/unsamflow_hip_convepi.h"
+#include "../../include/unsamflow_hip_fakeobj.h"
 #include "../../include/unsamflow_hip_hg.h"
 #include "../../include/unsamflow_hip_segpool.h"
 #include "usf_common.h"
@@ -82,9 +83,11 @@ static int finish(const char* fn, hipError_t e, hipStream_t s) {
   if (e == hipSuccess && sync_check_on(s)) {
     e = hipStreamSynchronize(s);
     if (e != hipSuccess) fprintf(stderr, "[usf] %s: fault after launch: %s\n", fn, hipGetErrorString(e));
-    // a bad segment id is the caller's data, not a failed launch: left for usf_device_errors
+    // a bad segment id or cache slot is the caller's data, not a failed launch: left for usf_device_errors
     const int flags =
-        e == hipSuccess ? device_errors(s, true, ~(USF_DEVERR_SEGPOOL_BAD_ID | USF_DEVERR_HG_BAD_ID)) : 0;
+        e == hipSuccess
+            ? device_errors(s, true, ~(USF_DEVERR_SEGPOOL_BAD_ID | USF_DEVERR_HG_BAD_ID | USF_DEVERR_FAKEOBJ_BAD_SLOT))
+            : 0;
     if (flags > 0) {
       fprintf(stderr, "[usf] %s: device error flags 0x%x\n", fn, flags);
       set_error("%s: device error flags 0x%x", fn, flags);
@@ -839,6 +842,84 @@ int usf_ar_loss_bwd_f32(const float* pred, const float* target, long long target
   return finish(fn,
                 ar_loss_bwd_launch(pred, target, target_bstride, target_cstride, target_rstride, noc, noc_bstride,
                                    noc_rstride, coef, grad_loss, grad_pred, B, H, W, eps, q, (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+// ------------------------------------------------ unsamflow_hip_fakeobj.h --
+int usf_fakeobj_api_version(void) { return USF_FAKEOBJ_API_VERSION; }
+
+// shape, flow stride and cache size of both fake-object entries
+static bool check_fakeobj(const char* fn, int B, int H, int W, long long fbs, int cache_size) {
+  if (!check_ar_dims(fn, B, 6, H, W)) return false;
+  if (B > 65535) {
+    set_error("%s: B=%d > 65535", fn, B);
+    return false;
+  }
+  if (fbs < 2LL * H * W && B > 1) {
+    set_error("%s: flow batch stride %lld < 2*H*W", fn, fbs);
+    return false;
+  }
+  if (cache_size < 1) {
+    set_error("%s: cache_size=%d (need >= 1)", fn, cache_size);
+    return false;
+  }
+  return true;
+}
+
+int usf_fakeobj_paste_crop_f32(const float* img1, const float* img2, const float* flow, long long flow_bstride,
+                               const float* noc, const float* cache_mask, const float* cache_img,
+                               const float* cache_motion, const int* slot, const float* param, float* imgs_ot,
+                               float* flow_ot, float* noc_ot, int B, int H, int W, int K, int cache_size, int y0,
+                               int x0, int ch, int cw, void* stream) {
+  clear_error();
+  const char* fn = "usf_fakeobj_paste_crop_f32";
+  if (!check_fakeobj(fn, B, H, W, flow_bstride, cache_size)) return USF_EINVAL;
+  if (K < 1 || K > USF_FAKEOBJ_MAX_K) {
+    set_error("%s: K=%d outside [1, %d]", fn, K, USF_FAKEOBJ_MAX_K);
+    return USF_EINVAL;
+  }
+  if (y0 < 0 || x0 < 0 || ch < 1 || cw < 1 || (long long)y0 + ch > H || (long long)x0 + cw > W) {
+    set_error("%s: crop window y0=%d x0=%d %dx%d outside the %dx%d image", fn, y0, x0, ch, cw, H, W);
+    return USF_EINVAL;
+  }
+  if (!img1 || !img2 || !flow || !noc || !cache_mask || !cache_img || !cache_motion || !slot || !param) {
+    set_error("%s: null input pointer", fn);
+    return USF_EINVAL;
+  }
+  if (!imgs_ot || !flow_ot || !noc_ot) {
+    set_error("%s: null output pointer", fn);
+    return USF_EINVAL;
+  }
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn,
+                fakeobj_paste_crop_launch(img1, img2, flow, flow_bstride, noc, cache_mask, cache_img, cache_motion, slot,
+                                          param, imgs_ot, flow_ot, noc_ot, B, H, W, K, cache_size, y0, x0, ch, cw,
+                                          (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+int usf_fakeobj_push_partials(int B, int H, int W) {
+  return (B > 0 && H > 0 && W > 0) ? fakeobj_push_partials(B, H, W) : 0;
+}
+
+int usf_fakeobj_push_f32(const float* obj_mask, const float* img, const float* flow, long long flow_bstride,
+                         const int* slot, float* cache_mask, float* cache_img, float* cache_motion, float* partials,
+                         int B, int H, int W, int cache_size, void* stream) {
+  clear_error();
+  const char* fn = "usf_fakeobj_push_f32";
+  if (!check_fakeobj(fn, B, H, W, flow_bstride, cache_size)) return USF_EINVAL;
+  if (!obj_mask || !img || !flow || !slot) {
+    set_error("%s: null input pointer", fn);
+    return USF_EINVAL;
+  }
+  if (!cache_mask || !cache_img || !cache_motion || !partials) {
+    set_error("%s: null output pointer", fn);
+    return USF_EINVAL;
+  }
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn,
+                fakeobj_push_launch(obj_mask, img, flow, flow_bstride, slot, cache_mask, cache_img, cache_motion,
+                                    partials, B, H, W, cache_size, (hipStream_t)stream),
                 (hipStream_t)stream);
 }
 

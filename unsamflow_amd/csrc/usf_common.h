@@ -214,6 +214,18 @@ hipError_t hg_loss_fwd_launch(const float* flow, long long fbs, const float* seg
 hipError_t hg_loss_bwd_launch(const float* flow, long long fbs, const float* seg, const int* records,
                               const float* gloss, float* gflow, int B, int H, int W, hipStream_t s);
 
+// fakeobj.hip: the key-object augmentation (paste + crop from the device cache, push into it)
+int fakeobj_device_errors(bool clear);  // this code object's flags (device_errors() adds them)
+hipError_t fakeobj_paste_crop_launch(const float* img1, const float* img2, const float* flow, long long fbs,
+                                     const float* noc, const float* cmask, const float* cimg, const float* cmotion,
+                                     const int* slot, const float* param, float* imgs_ot, float* flow_ot,
+                                     float* noc_ot, int B, int H, int W, int K, int cache_size, int y0, int x0, int ch,
+                                     int cw, hipStream_t s);
+int fakeobj_push_partials(int B, int H, int W);
+hipError_t fakeobj_push_launch(const float* mask, const float* img, const float* flow, long long fbs, const int* slot,
+                               float* cmask, float* cimg, float* cmotion, float* partials, int B, int H, int W,
+                               int cache_size, hipStream_t s);
+
 // convepi.hip: the conv epilogues (bias + LeakyReLU in place; their backward with the bias gradient)
 long long convepi_bwd_workspace(int B, int C, int H, int W);  // floats; -1: shape not taken
 hipError_t convepi_fwd_launch(float* y, const float* bias, int B, int C, int H, int W, float slope, hipStream_t s);

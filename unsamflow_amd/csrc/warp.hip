@@ -28,6 +28,7 @@
 #include "interp_tap.h"
 #include "scatter_rows.h"
 #include "usf_common.h"
+#include "../../include/unsamflow_hip_fakeobj.h"
 #include "../../include/unsamflow_hip_hg.h"
 #include "../../include/unsamflow_hip_segpool.h"
 #include "warp_tap.h"
@@ -1312,10 +1313,11 @@ int device_errors(hipStream_t s, bool clear, int mask) {
   if (hipStreamSynchronize(s) != hipSuccess) return -1;
   const int v = read_clear_flags(HIP_SYMBOL(g_dev_errors), clear, mask);
   if (v < 0) return -1;
-  // segpool.hip and hg.hip keep their own flag words (one code object per source file)
+  // segpool.hip, hg.hip and fakeobj.hip keep their own flag words (one code object per source file)
   const int sp = (mask & USF_DEVERR_SEGPOOL_BAD_ID) ? segpool_device_errors(clear) : 0;
   const int hg = (mask & USF_DEVERR_HG_BAD_ID) ? hg_device_errors(clear) : 0;
-  return (sp < 0 || hg < 0) ? -1 : (v | sp | hg);
+  const int fo = (mask & USF_DEVERR_FAKEOBJ_BAD_SLOT) ? fakeobj_device_errors(clear) : 0;
+  return (sp < 0 || hg < 0 || fo < 0) ? -1 : (v | sp | hg | fo);
 }
 
 hipError_t warp_fwd_launch(const float* x, const float* flow, long long fbs, float* out, int B,

@@ -20,7 +20,11 @@ epochs 50-200) the step adds the ARFlow branch of kitti_trainer_ar.py:137-249:
 the detached first-pass flow and its visibility mask are transformed by random
 affine maps together with the frames (unsamflow_amd.ar), a second pass
 (with_bk=False) on the transformed frames is held to the transformed flow by
-the AR loss, and a third pass does the same on a random crop.
+the AR loss, and a third pass does the same on a random crop. With
+``cfg.train.key_obj_aug`` (config.*_aug(), *_aug_hg(), the reference's epochs
+150-200) the third pass's inputs first get ``key_obj_count`` rounds of objects
+from a device-resident cache pasted in, and the step's own key objects are
+pushed into that cache (unsamflow_amd.fake_object, kitti_trainer_ar.py:192-262).
 
 The per-step host syncs of the reference's logging (``loss.item()``,
 kitti_trainer_ar.py:284-293) are not part of the step.
@@ -62,13 +66,38 @@ def synthetic_pair(B: int, H: int, W: int, device, seed: int = 42, with_seg: boo
     return img1, img2, segs[0], segs[1]
 
 
+def synthetic_key_objects(B: int, H: int, W: int, device, seed: int = 42, p_invalid: float = 0.25):
+    """Key-object masks as the loader hands them over: (mask [B,1,H,W] float,
+    valid [B] host bool). A valid sample holds one binary ellipse or rectangle
+    lying inside the image, of half-sizes H/8..H/4 by W/10..W/5 (an ellipse of
+    the smallest covers 3.9 % of the image, above the loader's 0.5 % floor); an
+    invalid one holds the reference's NaN placeholder."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    valid = torch.rand(B, generator=g) >= p_invalid
+    ys = torch.arange(H, dtype=torch.float32).view(H, 1)
+    xs = torch.arange(W, dtype=torch.float32).view(1, W)
+    mask = torch.full((B, 1, H, W), float("nan"))
+    for b in range(B):
+        u = torch.rand(5, generator=g)
+        ry = max(1.0, float(H / 8 + u[0] * H / 8))
+        rx = max(1.0, float(W / 10 + u[1] * W / 10))
+        cy = ry + float(u[2]) * max(0.0, H - 1 - 2 * ry)
+        cx = rx + float(u[3]) * max(0.0, W - 1 - 2 * rx)
+        dy, dx = (ys - cy).abs() / ry, (xs - cx).abs() / rx
+        inside = (dy * dy + dx * dx <= 1.0) if float(u[4]) < 0.5 else ((dy <= 1.0) & (dx <= 1.0))
+        if bool(valid[b]):
+            mask[b, 0] = inside.float()
+    return mask.to(device), valid
+
+
 class TrainStep:
     """One PWCLite fwd(with_bk) + unFlowLoss + bwd + clip + Adam + OneCycleLR step."""
 
     def __init__(self, cfg, device, ddp: bool = False, corr_module=None, warp_fn: Callable | None = None,
                  loss_kwargs: dict | None = None, fused_adam: bool | None = None, seed: int = 42,
                  channels_last: bool = False, occ_backward_fn: Callable | None = None,
-                 capturable: bool = False, fused_ar: bool = True):
+                 capturable: bool = False, fused_ar: bool = True, fused_fake_object: bool = True,
+                 obj_cache_size: int = 100):
         torch.manual_seed(seed)
         self.cfg = cfg
         self.device = torch.device(device)
@@ -118,8 +147,19 @@ class TrainStep:
             self.ar_generator = torch.Generator(device="cpu").manual_seed(seed)
             self.sp_transform = RandomAffineFlow(t.st_cfg, addnoise=t.st_cfg.add_noise,
                                                  generator=self.ar_generator, fused=self.fused_ar)
+        # the key-object augmentation of the third pass (kitti_trainer_ar.py:192-262): the cache lives on the
+        # device, its slot choices and the pop's draws come from the step's host generator
+        self.key_obj_aug = self.run_ot and bool(t.get("key_obj_aug", False))
+        self.obj_cache = None
+        if self.key_obj_aug:
+            from .fake_object import ObjectCache
 
-    def forward_loss(self, img1, img2, full_seg1=None, full_seg2=None, img1_ph=None, img2_ph=None):
+            # fused_fake_object: the HIP paste + crop and push on a ROCm device; False: the torch composition
+            self.fused_fake_object = None if fused_fake_object else False
+            self.obj_cache = ObjectCache(obj_cache_size, self.device, generator=self.ar_generator)
+
+    def forward_loss(self, img1, img2, full_seg1=None, full_seg2=None, img1_ph=None, img2_ph=None,
+                     key_obj_mask=None, key_obj_valid=None):
         res = self.model(img1, img2, full_seg1, full_seg2, with_bk=True)
         flows = [torch.cat([a, b], 1) for a, b in zip(res["flows_12"], res["flows_21"])]
         kw = {}
@@ -129,14 +169,20 @@ class TrainStep:
         loss = loss.mean()
         if self.has_ar:
             loss = loss + self._ar_branch(res["flows_12"][0].detach(), vis1.detach(),
-                                          img1 if img1_ph is None else img1_ph, img2 if img2_ph is None else img2_ph)
+                                          img1 if img1_ph is None else img1_ph, img2 if img2_ph is None else img2_ph,
+                                          key_obj_mask, key_obj_valid)
         return loss, flows
 
-    def _ar_branch(self, flow_ori, noc_ori, img1, img2):
+    def _ar_branch(self, flow_ori, noc_ori, img1, img2, key_obj_mask=None, key_obj_valid=None):
         """w_ar * (l_atst + l_ot): the second pass on the spatially transformed
         frames and the third on a random crop, each held to the first pass's
-        (transformed / cropped) flow where it was visible."""
-        from .ar import ar_loss, random_crop
+        (transformed / cropped) flow where it was visible. With key_obj_aug and
+        a full object cache the third pass's inputs get key_obj_count rounds of
+        cached objects pasted in before the crop; afterwards the step's own key
+        objects (``key_obj_mask`` [B,1,H,W] on the device, ``key_obj_valid`` [B]
+        host bool) are pushed. Host draws in order: the pop, the crop offsets (x
+        before y), the push's slots. Nothing here reads the device from the host."""
+        from .ar import ar_loss, crop_offsets, random_crop
 
         t = self.cfg.train
         total = 0.0
@@ -153,20 +199,33 @@ class TrainStep:
             total = total + t.w_ar * l_atst
             self.l_atst = l_atst.detach()
         if self.run_ot:
-            imgs, flow_ot, noc_ot = random_crop(torch.cat([img1, img2], 1), flow_ori, noc_ori, t.ot_size,
-                                                self.ar_generator)
+            popped = None
+            if self.key_obj_aug:  # None (and no draw) until the cache is full
+                popped = self.obj_cache.pop(img1.shape[0] * int(t.key_obj_count), with_aug=True)
+            if popped is None:
+                imgs, flow_ot, noc_ot = random_crop(torch.cat([img1, img2], 1), flow_ori, noc_ori, t.ot_size,
+                                                    self.ar_generator)
+            else:
+                from .fake_object import paste_and_crop
+
+                offsets = crop_offsets(*img1.shape[-2:], t.ot_size, self.ar_generator)
+                imgs, flow_ot, noc_ot = paste_and_crop(img1, img2, flow_ori, noc_ori, self.obj_cache, *popped,
+                                                       tuple(t.ot_size), offsets, fused=self.fused_fake_object)
             pred = self.model(imgs[:, :3], imgs[:, 3:6], with_bk=False)["flows_12"][0]
             l_ot = ar_loss(pred, flow_ot, noc_ot, t.ar_eps, t.ar_q, fused=self.fused_ar)
             total = total + t.w_ar * l_ot
             self.l_ot = l_ot.detach()
+            if self.key_obj_aug and key_obj_mask is not None:
+                self.obj_cache.push(key_obj_mask, img1, flow_ori, key_obj_valid, fused=self.fused_fake_object)
         return total
 
-    def __call__(self, img1, img2, full_seg1=None, full_seg2=None, img1_ph=None, img2_ph=None):
+    def __call__(self, img1, img2, full_seg1=None, full_seg2=None, img1_ph=None, img2_ph=None, key_obj_mask=None,
+                 key_obj_valid=None):
         ev = None
         if self.phase_events is not None:
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
             ev[0].record()
-        loss, _ = self.forward_loss(img1, img2, full_seg1, full_seg2, img1_ph, img2_ph)
+        loss, _ = self.forward_loss(img1, img2, full_seg1, full_seg2, img1_ph, img2_ph, key_obj_mask, key_obj_valid)
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         if ev is not None:

@@ -864,6 +864,105 @@ def ar_loss_backward(pred, target, noc, coef, grad_loss, eps: float = 0.0, q: fl
     return gpred
 
 
+def _fakeobj_cache(cache_mask, cache_img, H, W):
+    _require_device_f32("cache_mask", cache_mask)
+    _require_device_f32("cache_img", cache_img)
+    n = cache_mask.shape[0] if cache_mask.dim() == 4 else 0
+    if n < 1 or tuple(cache_mask.shape) != (n, 1, H, W) or tuple(cache_img.shape) != (n, 3, H, W):
+        raise ValueError(f"cache_mask / cache_img must be [N,1,{H},{W}] / [N,3,{H},{W}], got "
+                         f"{tuple(cache_mask.shape)} / {tuple(cache_img.shape)}")
+    if not cache_mask.is_contiguous() or not cache_img.is_contiguous():
+        raise ValueError("the object cache must be contiguous (it is addressed in place)")
+    return n
+
+
+def _fakeobj_table(name, t, shape, dtype, device):
+    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != device
+            or not t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous {dtype} {tuple(shape)} tensor on {device}")
+
+
+def fakeobj_paste_crop(img1, img2, flow, noc, cache_mask, cache_img, cache_motion, slots, params, crop_sz, offsets):
+    """K rounds of add_fake_object on objects read in place from the device
+    cache, then the crop, in one launch (usf_fakeobj_paste_crop_f32). img1, img2
+    [B,3,H,W], flow [B,2,H,W] (a channel slice is used in place), noc [B,1,H,W];
+    slots [K*B] int32 and params [K*B,4] float32 (sx, sy, flip, 0: the factors
+    on the slot's cached motion and the x mirror) on the device; crop_sz = (ch, cw), offsets = (y0, x0) -> (imgs_ot [B,6,ch,cw], flow_ot
+    [B,2,ch,cw], noc_ot [B,1,ch,cw])."""
+    for n, t in (("img1", img1), ("img2", img2), ("flow", flow), ("noc", noc), ("cache_motion", cache_motion)):
+        _require_device_f32(n, t)
+    B, C, H, W = _nchw("img1", img1)
+    if C != 3 or tuple(img2.shape) != (B, 3, H, W):
+        raise ValueError(f"img1 / img2 must be [B,3,H,W], got {tuple(img1.shape)} / {tuple(img2.shape)}")
+    if H < 2 or W < 2:
+        raise ValueError(f"the object insertion needs H, W >= 2, got {(H, W)}")
+    if tuple(noc.shape) != (B, 1, H, W):
+        raise ValueError(f"noc {tuple(noc.shape)} does not match {(B, 1, H, W)}")
+    dev = img1.device
+    size = _fakeobj_cache(cache_mask, cache_img, H, W)
+    _fakeobj_table("cache_motion", cache_motion, (size, 2), torch.float32, dev)
+    n = slots.numel() if isinstance(slots, torch.Tensor) else 0
+    K = n // B
+    if n != K * B or not 1 <= K <= _lib.FAKEOBJ_MAX_K:
+        raise ValueError(f"slots must hold K*B entries with 1 <= K <= {_lib.FAKEOBJ_MAX_K}, got {n} for B={B}")
+    _fakeobj_table("slots", slots, (n,), torch.int32, dev)
+    _fakeobj_table("params", params, (n, 4), torch.float32, dev)
+    (ch, cw), (y0, x0) = (int(v) for v in crop_sz), (int(v) for v in offsets)
+    if y0 < 0 or x0 < 0 or ch < 1 or cw < 1 or y0 + ch > H or x0 + cw > W:
+        raise ValueError(f"crop {(ch, cw)} at {(y0, x0)} lies outside the image {(H, W)}")
+    if any(t.device != dev for t in (img2, flow, noc, cache_mask, cache_img)):
+        raise ValueError("the object insertion's tensors are on different devices")
+    a, b_, nc = img1.contiguous(), img2.contiguous(), noc.contiguous()
+    fv, fbs = _flow_view(flow, B, H, W)
+    outs = (torch.empty((B, 6, ch, cw), device=dev, dtype=torch.float32),
+            torch.empty((B, 2, ch, cw), device=dev, dtype=torch.float32),
+            torch.empty((B, 1, ch, cw), device=dev, dtype=torch.float32))
+    lib = _lib.load()
+    # algorithmic bytes: 9 base planes in and out; per object 4 floats at the pixel and 4 at the shifted position
+    nbytes = 4 * B * ch * cw * (18 + 8 * K)
+    _args = (a.data_ptr(), b_.data_ptr(), fv.data_ptr(), fbs, nc.data_ptr(), cache_mask.data_ptr(),
+             cache_img.data_ptr(), cache_motion.data_ptr(), slots.data_ptr(), params.data_ptr(),
+             *[t.data_ptr() for t in outs], B, H, W, K, size, y0, x0, ch, cw, _lib.stream_handle(dev),)
+    with torch.cuda.device(dev), _kt.timed("fakeobj_paste_crop", (B, H, W, K, ch, cw), dev, nbytes):
+        rc = lib.usf_fakeobj_paste_crop_f32(*_args)
+    _lib.check(rc, "usf_fakeobj_paste_crop_f32")
+    return outs
+
+
+def fakeobj_push(obj_mask, img, flow, slots, cache_mask, cache_img, cache_motion):
+    """Copy every sample b with slots[b] >= 0 into its cache slot and write its
+    masked mean flow into cache_motion (usf_fakeobj_push_f32; deterministic).
+    obj_mask [B,1,H,W], img [B,3,H,W], flow [B,2,H,W] (a channel slice is used in
+    place), slots [B] int32 on the device (-1: skip the sample); the cache
+    tensors are written in place."""
+    for n, t in (("obj_mask", obj_mask), ("img", img), ("flow", flow), ("cache_motion", cache_motion)):
+        _require_device_f32(n, t)
+    B, C, H, W = _nchw("img", img)
+    if C != 3 or tuple(obj_mask.shape) != (B, 1, H, W):
+        raise ValueError(f"obj_mask / img must be [B,1,H,W] / [B,3,H,W], got {tuple(obj_mask.shape)} / "
+                         f"{tuple(img.shape)}")
+    if H < 2 or W < 2:
+        raise ValueError(f"the object cache needs H, W >= 2, got {(H, W)}")
+    dev = img.device
+    size = _fakeobj_cache(cache_mask, cache_img, H, W)
+    _fakeobj_table("cache_motion", cache_motion, (size, 2), torch.float32, dev)
+    _fakeobj_table("slots", slots, (B,), torch.int32, dev)
+    if any(t.device != dev for t in (obj_mask, flow, cache_mask, cache_img)):
+        raise ValueError("the object cache's tensors are on different devices")
+    m, im = obj_mask.contiguous(), img.contiguous()
+    fv, fbs = _flow_view(flow, B, H, W)
+    lib = _lib.load()
+    partials = torch.empty(lib.usf_fakeobj_push_partials(B, H, W), device=dev, dtype=torch.float32)
+    # algorithmic bytes: mask and frame read and written once, the flow read once
+    nbytes = 4 * B * H * W * (4 + 2 + 4)
+    _args = (m.data_ptr(), im.data_ptr(), fv.data_ptr(), fbs, slots.data_ptr(), cache_mask.data_ptr(),
+             cache_img.data_ptr(), cache_motion.data_ptr(), partials.data_ptr(), B, H, W, size,
+             _lib.stream_handle(dev),)
+    with torch.cuda.device(dev), _kt.timed("fakeobj_push", (B, H, W), dev, nbytes):
+        rc = lib.usf_fakeobj_push_f32(*_args)
+    _lib.check(rc, "usf_fakeobj_push_f32")
+
+
 def _segpool_args(proj, seg, num_segments):
     _require_device_f32("proj", proj)
     _require_device_f32("seg", seg)
