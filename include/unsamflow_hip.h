@@ -64,6 +64,18 @@
  *     failed") (correlation_cuda.cc:80-82, :160-162); the Python layer raises
  *     RuntimeError with this string.
  *   - Nullable gradient outputs mean "not needed" (ctx.needs_input_grad).
+ *   - Alignment: the kernels pick their 8- and 16-byte accesses from the shape
+ *     (W % 4 == 0, H*W % 4 == 0, a batch stride % 4 == 0), not from the address,
+ *     so every entry point states the alignment of each pointer ("Alignment:"
+ *     in its comment) and returns USF_EINVAL, naming the parameter, for a
+ *     pointer that misses it; nothing is launched. 16 bytes is what any fresh
+ *     allocation has; 4 bytes marks the pointers that may be slices of a
+ *     larger tensor (only 4-byte accesses go through them). A batch stride
+ *     that is no multiple of 4 elements is allowed wherever a stride is a
+ *     parameter: the kernels then take their 4-byte paths.
+ *   - Scratch, workspace and partials buffers need no initialisation unless
+ *     their entry says "ZERO when first passed"; their contents are undefined
+ *     after the call. Outputs are overwritten entirely.
  */
 #ifndef UNSAMFLOW_HIP_H
 #define UNSAMFLOW_HIP_H
@@ -102,7 +114,8 @@ const char* usf_last_error_string(void);
  *       (1/C) * sum_c x1[b,c,y,x] * X2(b,c,y+dy,x+dx),  X2 = 0 outside HxW
  * x1, x2: [B,C,H,W]; out: [B,(2d+1)^2,H,W]. 1 <= d <= 4.
  * Semantics of correlation_native.py:13-23 == correlation_cuda forward with
- * pad_size=d, kernel_size=1, stride1=stride2=1 (correlation_cuda.cc:19-34). */
+ * pad_size=d, kernel_size=1, stride1=stride2=1 (correlation_cuda.cc:19-34).
+ * Alignment: x1, x2, out 16 bytes. */
 int usf_corr_fwd_f32(const float* x1, const float* x2, float* out,
                      int B, int C, int H, int W, int d, void* stream);
 
@@ -110,7 +123,8 @@ int usf_corr_fwd_f32(const float* x1, const float* x2, float* out,
  *   gx1[b,c,y,x] = (1/C) sum_k gout[b,k,y,x]       * X2(b,c,y+dy_k,x+dx_k)
  *   gx2[b,c,y,x] = (1/C) sum_k G(b,k,y-dy_k,x-dx_k) * X1(b,c,y-dy_k,x-dx_k)
  * gx1 / gx2 may be NULL (not needed). Outputs are overwritten (not
- * accumulated) and the result is deterministic (no atomics). */
+ * accumulated) and the result is deterministic (no atomics).
+ * Alignment: x1, x2, gout, gx1, gx2 16 bytes. */
 int usf_corr_bwd_f32(const float* x1, const float* x2, const float* gout,
                      float* gx1, float* gx2,
                      int B, int C, int H, int W, int d, void* stream);
@@ -133,7 +147,11 @@ int usf_corr_bwd_f32(const float* x1, const float* x2, const float* gout,
  * out [B][2d+1][H][ceil(W/4)], bit 4*dx + (x % 4) of word
  * (b, dy, y, x/4) = (out at (b, dy*(2d+1)+dx, y, x) > 0). Pass it to
  * usf_corr_bwd_ex_f32 to apply the LeakyReLU derivative without re-reading
- * the activated output. */
+ * the activated output. Every word of act_mask is written. workspace needs no
+ * initialisation and is scratch after return.
+ * Alignment: x1, x2, act_mask, workspace 16 bytes; out (a channel slice) 16
+ * bytes when H*W % 4 == 0 -- which a slice of a 16-byte aligned NCHW buffer
+ * always has -- and 4 bytes otherwise. */
 int usf_corr_fwd_ex_f32(const float* x1, const float* x2, float* out, long long out_bstride,
                         int act, float slope, unsigned long long* act_mask, float* workspace,
                         long long workspace_floats, int B, int C, int H, int W, int d,
@@ -153,7 +171,10 @@ long long usf_corr_fwd_workspace(int B, int C, int H, int W, int d);
  * usf_corr_bwd_ex_scratch(B,C,H,W,d) floats; unused when act_out is NULL).
  * With act_mask != NULL (the forward's sign mask) the same
  * derivative is applied inside the backward kernel's gradient loads instead:
- * act_out and scratch are ignored and no extra pass runs. */
+ * act_out and scratch are ignored and no extra pass runs. scratch needs no
+ * initialisation and is scratch after return.
+ * Alignment: x1, x2, act_mask, scratch, gx1, gx2 16 bytes; gout and act_out
+ * (channel slices) 16 bytes when H*W % 4 == 0, 4 bytes otherwise. */
 int usf_corr_bwd_ex_f32(const float* x1, const float* x2, const float* gout, long long g_bstride,
                         const float* act_out, const unsigned long long* act_mask, float slope,
                         float* scratch, float* gx1, float* gx2, int B, int C, int H, int W, int d,
@@ -164,7 +185,8 @@ long long usf_corr_bwd_ex_scratch(int B, int C, int H, int W, int d);
 
 /* Bilinear backward warp (flow_warp), align_corners=True.
  * x: [B,C,H,W]; flow: [B,2,H,W] with batch stride flow_bstride (elements);
- * out: [B,C,H,W]. pad_mode: USF_PAD_BORDER or USF_PAD_ZEROS. */
+ * out: [B,C,H,W]. pad_mode: USF_PAD_BORDER or USF_PAD_ZEROS.
+ * Alignment: x, out 16 bytes; flow 4 bytes (a channel slice). */
 int usf_warp_fwd_f32(const float* x, const float* flow, long long flow_bstride,
                      float* out, int B, int C, int H, int W, int pad_mode,
                      void* stream);
@@ -174,14 +196,17 @@ int usf_warp_fwd_f32(const float* x, const float* flow, long long flow_bstride,
  * align_corners=True); x2_warp = flow_warp(x2, flow)). coarse_flow: dense
  * [B,2,H/2,W/2] (H, W even); up_flow: dense [B,2,H,W], written (the same numbers
  * as usf_flow_upsample_f32 with factor 2); out: [B,C,H,W] = usf_warp_fwd_f32(x,
- * up_flow). */
+ * up_flow).
+ * Alignment: x, coarse_flow, up_flow, out 16 bytes. */
 int usf_warp_fwd_up_f32(const float* x, const float* coarse_flow, float* up_flow, float* out, int B, int C, int H,
                         int W, int pad_mode, void* stream);
 
 /* Backward of usf_warp_fwd_f32. gout: [B,C,H,W] dense.
  * gx: [B,C,H,W] or NULL; overwritten (the library zeroes it, then scatters
  *     with fp32 atomics: summation order not fixed).
- * gflow: [B,2,H,W] dense or NULL; overwritten, deterministic. */
+ * gflow: [B,2,H,W] dense or NULL; overwritten, deterministic.
+ * Alignment (all three warp backward forms): x, gout, gx, gflow 16 bytes; flow
+ * 4 bytes (a channel slice); workspace 16 bytes. */
 int usf_warp_bwd_f32(const float* x, const float* flow, long long flow_bstride,
                      const float* gout, float* gx, float* gflow,
                      int B, int C, int H, int W, int pad_mode, void* stream);
@@ -231,13 +256,15 @@ long long usf_warp_bwd_persist_workspace(int B, int C, int H, int W);
  * and adds (1-|x-cx|)*(1-|y-cy|) to each of its 4 integer neighbours inside
  * the image. map: [B,1,H,W] dense, overwritten (zeroed by the call on the
  * stream, then accumulated with fp32 atomics: summation order not fixed).
- * flow: [B,2,H,W] with batch stride flow_bstride. */
+ * flow: [B,2,H,W] with batch stride flow_bstride.
+ * Alignment: flow 4 bytes (a channel slice); map 16 bytes. */
 int usf_splat_map_f32(const float* flow, long long flow_bstride, float* map,
                       int B, int H, int W, int absolute, void* stream);
 
 /* Occlusion mask from the backward flow (get_occu_mask_backward,
  * warp_utils.py:120-126): occ = clamp(splat_map(flow21), 0, 1) < th ? 1 : 0.
- * occ: [B,1,H,W] dense, overwritten. */
+ * occ: [B,1,H,W] dense, overwritten.
+ * Alignment: flow21 4 bytes (a channel slice); occ 16 bytes. */
 int usf_occ_backward_f32(const float* flow21, long long flow_bstride, float* occ,
                          int B, int H, int W, float th, void* stream);
 
@@ -245,7 +272,8 @@ int usf_occ_backward_f32(const float* flow21, long long flow_bstride, float* occ
  * map, the caller's persistent [B,1,H,W] fp32 buffer (map_bytes >= 4*B*H*W),
  * which must be ZERO when first passed; the threshold pass is its only reader
  * and zeroes it again, so no fill runs per call (graph-replay safe). One
- * stream at a time per map. occ: [B,1,H,W] dense, overwritten. */
+ * stream at a time per map. occ: [B,1,H,W] dense, overwritten.
+ * Alignment: flow21 4 bytes; occ, map 16 bytes. */
 int usf_occ_backward_persist_f32(const float* flow21, long long flow_bstride, float* occ, float* map,
                                  long long map_bytes, int B, int H, int W, float th, void* stream);
 
@@ -258,7 +286,8 @@ int usf_occ_backward_persist_f32(const float* flow21, long long flow_bstride, fl
  * vis: [2,B,1,H,W] dense, overwritten: vis[0] = vis_mask1, vis[1] = vis_mask2
  * (1 or 0; masks equal get_occu_mask_backward's except where a splat sum lies
  * within fp32 rounding of th, whose summation order is not fixed). One stream
- * at a time per map. */
+ * at a time per map.
+ * Alignment: flow4 4 bytes; vis, map 16 bytes. */
 int usf_occ_vis_pair_persist_f32(const float* flow4, long long flow_bstride, float* vis, float* map,
                                  long long map_bytes, int B, int H, int W, float th, void* stream);
 
@@ -267,7 +296,8 @@ int usf_occ_vis_pair_persist_f32(const float* flow4, long long flow_bstride, flo
  *   w21 = flow_warp(flow21, flow12, pad="zeros"); d = flow12 + w21
  *   occ = |d|^2 > scale * (|flow12|^2 + |w21|^2) + bias ? 1 : 0
  * flow12, flow21: [B,2,H,W] with batch strides (channel slices allowed);
- * occ: [B,1,H,W] dense, overwritten. Each sum/product rounded as torch does. */
+ * occ: [B,1,H,W] dense, overwritten. Each sum/product rounded as torch does.
+ * Alignment: flow12, flow21 4 bytes (channel slices); occ 16 bytes. */
 int usf_occ_bidirection_f32(const float* flow12, long long flow12_bstride, const float* flow21,
                             long long flow21_bstride, float* occ, int B, int H, int W,
                             float scale, float bias, void* stream);
@@ -285,7 +315,11 @@ int usf_occ_bidirection_f32(const float* flow12, long long flow12_bstride, const
  * [B,4,H,W] dense, overwritten with the per-pixel flow-gradient basis
  * {A_x, A_y, S_x, S_y}: dL/dflow = c_l1 * A + c_ssim * S (the L1 and the SSIM
  * parts; L is linear in both), computed in the same pass. Deterministic
- * (fixed-order sums). usf_photo_loss_partials(B,H,W) is per direction. */
+ * (fixed-order sums). usf_photo_loss_partials(B,H,W) is per direction.
+ * partials needs no initialisation and is scratch after return.
+ * Alignment (every usf_photo_loss_*_fwd entry, per scale in the pyramid form):
+ * the images, the masks, partials and grad_basis 16 bytes; flow 4 bytes (a
+ * channel slice); out 4 bytes. */
 int usf_photo_loss_partials(int B, int H, int W);
 int usf_photo_loss_fwd_f32(const float* src, const float* tgt, const float* mask,
                            const float* flow, long long flow_bstride, float* partials,
@@ -334,14 +368,17 @@ int usf_photo_loss_pyramid_bwd_f32(int nscale, const float* const* grad_basis, c
  * grad_flow[:, 2d:2d+2] = (c_l1 * A + c_ssim * S) * grad_loss[d] per direction d.
  * grad_basis: the forward's [B,ndir,4,H,W] basis; coef: the forward's `out`
  * (3 * ndir floats, device); grad_loss: ndir device floats; grad_flow:
- * [B,2*ndir,H,W] dense, overwritten, deterministic. */
+ * [B,2*ndir,H,W] dense, overwritten, deterministic.
+ * Alignment (this and the pyramid backward, per scale): grad_basis, grad_flow
+ * 16 bytes; coef, grad_loss 4 bytes (they may be rows of a larger tensor). */
 int usf_photo_loss_bwd_f32(const float* grad_basis, const float* coef, const float* grad_loss,
                            float* grad_flow, int B, int H, int W, int ndir, void* stream);
 
 /* Decoder flow upsampling (pwclite.py:299-301 and the x4 output flows):
  *   out = F.interpolate(flow * factor, scale_factor=factor, mode="bilinear",
  *                       align_corners=True)
- * flow: [B,C,H,W] dense; out: [B,C,H*factor,W*factor] dense, overwritten. */
+ * flow: [B,C,H,W] dense; out: [B,C,H*factor,W*factor] dense, overwritten.
+ * Alignment (this and both backward forms): every pointer 16 bytes. */
 int usf_flow_upsample_f32(const float* flow, float* out, int B, int C, int H, int W,
                           int factor, void* stream);
 
@@ -364,7 +401,10 @@ int usf_flow_upsample_bwd_sum_f32(const float* grad_a, const float* grad_b, floa
  *   out[b,c,f*y+i,f*x+j] = sum_k w[b,k,i,j,y,x] * f * flow[b,c,y+ky-1,x+kx-1]
  * (k = 3 ky + kx, zero outside the image; mask_scale = 0.25 at :165).
  * flow: [B,2,H,W] dense; mask: [B,9*f*f,H,W] dense (the convs' raw output);
- * out: [B,2,f*H,f*W] dense, overwritten. */
+ * out: [B,2,f*H,f*W] dense, overwritten.
+ * Alignment (all four usf_convex_upsample_* entries, per level in the pyramid
+ * forms): every pointer 16 bytes -- out and grad_out move in 8- and 16-byte
+ * runs at every shape. */
 int usf_convex_upsample_f32(const float* flow, const float* mask, float* out, int B, int H, int W,
                             int factor, float mask_scale, void* stream);
 
@@ -375,7 +415,8 @@ long long usf_convex_upsample_bwd_scratch(int B, int H, int W);
 /* Its backward from grad_out [B,2,f*H,f*W]: grad_flow [B,2,H,W] and grad_mask
  * [B,9*f*f,H,W] w.r.t. the RAW mask (mask_scale applied), both dense,
  * overwritten, deterministic (no atomics); either may be NULL. scratch:
- * usf_convex_upsample_bwd_scratch floats when grad_flow is non-NULL. */
+ * usf_convex_upsample_bwd_scratch floats when grad_flow is non-NULL; it needs
+ * no initialisation and is scratch after return (the pyramid form's likewise). */
 int usf_convex_upsample_bwd_f32(const float* flow, const float* mask, const float* grad_out,
                                 float* grad_flow, float* grad_mask, float* scratch, int B, int H,
                                 int W, int factor, float mask_scale, void* stream);
@@ -407,7 +448,8 @@ int usf_convex_upsample_pyramid_bwd_f32(int nlevel, const float* const* flow, co
  * (H >> s, W >> s), mode="area"), flow_loss.py:128-129): out_s = mean of each
  * 2^s x 2^s block, summed in row-major order as torch's CPU kernel does
  * (bit-exact). x: [B,C,H,W] dense with H % 8 == 0 and W % 8 == 0; out1/2/3:
- * [B,C,H/2,W/2], [B,C,H/4,W/4], [B,C,H/8,W/8] dense, overwritten. */
+ * [B,C,H/2,W/2], [B,C,H/4,W/4], [B,C,H/8,W/8] dense, overwritten.
+ * Alignment: x, out1, out2, out3 16 bytes. */
 int usf_area_pyramid_f32(const float* x, float* out1, float* out2, float* out3, int B, int C,
                          int H, int W, void* stream);
 

@@ -45,7 +45,9 @@ int usf_ar_api_version(void);
  * img1, img2: [B,3,H,W] dense; flow: [B,2,H,W] with batch stride flow_bstride
  * (a dense [2,H,W] block per sample); mask: [B,1,H,W] dense; noise1, noise2:
  * NULL, or [B,3,H,W] dense, already scaled: img_t = clamp(img_t + noise, 0, 1).
- * Outputs dense, overwritten; they must not alias the inputs. H, W >= 2. */
+ * Outputs dense, overwritten; they must not alias the inputs. H, W >= 2.
+ * Alignment: img1, img2, mask, noise1, noise2 and the four outputs 16 bytes;
+ * flow (a channel slice) and theta 4 bytes. A misaligned pointer is USF_EINVAL. */
 int usf_ar_transform_f32(const float* img1, const float* img2, const float* flow,
                          long long flow_bstride, const float* mask, const float* theta,
                          const float* noise1, const float* noise2, float* img1_t, float* img2_t,
@@ -60,7 +62,9 @@ int usf_ar_transform_f32(const float* img1, const float* img2, const float* flow
  * caller scratch of usf_ar_loss_partials(B,H,W) floats. out: 2 floats =
  * {loss, c}, c = 1 / (2 B H W (D + 1e-7)) (what the backward needs). q > 0,
  * eps >= 0. Deterministic: per-workgroup sums, then a fixed-order fp64
- * finalisation; no atomics. */
+ * finalisation; no atomics. partials needs no initialisation and is scratch
+ * after return.
+ * Alignment: pred, target, noc (views), denom and out 4 bytes; partials 16 bytes. */
 int usf_ar_loss_partials(int B, int H, int W);
 int usf_ar_loss_fwd_f32(const float* pred, const float* target, long long target_bstride,
                         long long target_cstride, long long target_rstride, const float* noc,
@@ -71,7 +75,8 @@ int usf_ar_loss_fwd_f32(const float* pred, const float* target, long long target
 /* grad_pred = grad_loss * c * q (|d| + eps)^(q-1) sign(d) noc, d = pred - target,
  * sign(0) = 0: one dense pass recomputing from the forward's inputs. coef = the
  * forward's out; grad_loss: one float on the device; grad_pred: [B,2,H,W] dense,
- * overwritten. The gradient reaches pred only. */
+ * overwritten. The gradient reaches pred only.
+ * Alignment: pred, target, noc, coef, grad_loss 4 bytes; grad_pred 16 bytes. */
 int usf_ar_loss_bwd_f32(const float* pred, const float* target, long long target_bstride,
                         long long target_cstride, long long target_rstride, const float* noc,
                         long long noc_bstride, long long noc_rstride, const float* coef,

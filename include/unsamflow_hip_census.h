@@ -38,7 +38,11 @@ int usf_census_api_version(void);
  * {L, c_t} (c_t is what the backward needs). grad_basis: NULL (no gradient
  * wanted), or [B,2,H,W] dense, overwritten with the per-pixel flow-gradient
  * basis: dL/dflow = c_t * basis (L is linear in the census sum), computed in
- * the same pass. Deterministic (fixed-order sums, no atomics). */
+ * the same pass. Deterministic (fixed-order sums, no atomics). partials needs
+ * no initialisation and is scratch after return.
+ * Alignment (every usf_census_loss_*_fwd entry, per scale in the pyramid
+ * form): the images, the masks, partials and grad_basis 16 bytes; flow 4 bytes
+ * (a channel slice); out 4 bytes. A misaligned pointer is USF_EINVAL. */
 int usf_census_loss_partials(int B, int H, int W);
 int usf_census_loss_fwd_f32(const float* src, const float* tgt, const float* mask,
                             const float* flow, long long flow_bstride, float* partials,
@@ -59,7 +63,9 @@ int usf_census_loss_pair_fwd_f32(const float* im1, const float* im2, const float
 /* grad_flow = c_t * grad_basis * grad_loss per direction: grad_basis
  * [B,2*ndir,H,W], coef = the forward's out (2 floats per direction), grad_loss:
  * ndir floats on the device, grad_flow: [B,2*ndir,H,W] dense, overwritten.
- * ndir = 1 or 2. */
+ * ndir = 1 or 2.
+ * Alignment (this and the pyramid backward, per scale): grad_basis, grad_flow
+ * 16 bytes; coef, grad_loss 4 bytes. */
 int usf_census_loss_bwd_f32(const float* grad_basis, const float* coef, const float* grad_loss,
                             float* grad_flow, int B, int H, int W, int ndir, void* stream);
 

@@ -38,7 +38,8 @@ int usf_convepi_api_version(void);
 
 /* In place: y[b,c,:] = act(y[b,c,:] + bias[c]), act(v) = v > 0 ? v : v * slope,
  * the arithmetic of add_ followed by leaky_relu_ (bit-identical). slope == 1 is
- * no activation. y: [B,C,H,W] dense, 16-byte aligned; bias: [C]. slope > 0. */
+ * no activation. y: [B,C,H,W] dense, 16-byte aligned; bias: [C], 4-byte
+ * aligned. slope > 0. A misaligned pointer is USF_EINVAL. */
 int usf_convepi_fwd_f32(float* y, const float* bias, int B, int C, int H, int W, float slope, void* stream);
 
 /* Floats of `workspace` usf_convepi_bwd_f32 needs for the bias gradient of this
@@ -57,7 +58,8 @@ long long usf_convepi_bwd_workspace(int B, int C, int H, int W);
  * elements (>= C*H*W: a channel slice of a concat gradient), 4-byte aligned.
  * y, grad_in: dense, 16-byte aligned. grad_bias: [C], or NULL for no reduction
  * (slope != 1 only). workspace: usf_convepi_bwd_workspace floats (may be NULL
- * when that is 0 or grad_bias is NULL), contents undefined on return.
+ * when that is 0 or grad_bias is NULL), no initialisation needed, contents
+ * undefined on return. grad_bias, workspace: 4-byte aligned.
  * Deterministic: no atomics, the summation order depends on the shape only. */
 int usf_convepi_bwd_f32(const float* grad_out, long long gout_bstride, const float* y, float* grad_in,
                         float* grad_bias, float* workspace, long long workspace_floats, int B, int C, int H, int W,

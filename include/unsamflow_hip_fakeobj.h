@@ -67,7 +67,10 @@ int usf_fakeobj_api_version(void);
  * 1 <= K <= USF_FAKEOBJ_MAX_K, H, W >= 2, cache_size >= 1, B <= 65535, and the
  * window must lie inside the image (0 <= y0, y0 + ch <= H, ch >= 1; likewise x):
  * anything else is USF_EINVAL before any launch. A slot outside [0, cache_size)
- * skips that round of that sample and raises USF_DEVERR_FAKEOBJ_BAD_SLOT. */
+ * skips that round of that sample and raises USF_DEVERR_FAKEOBJ_BAD_SLOT.
+ * Alignment: img1, img2, noc and the three outputs 16 bytes; flow (a channel
+ * slice), the cache tensors (addressed in place, wherever the caller keeps
+ * them), slot and param 4 bytes. A misaligned pointer is USF_EINVAL. */
 int usf_fakeobj_paste_crop_f32(const float* img1, const float* img2, const float* flow, long long flow_bstride,
                                const float* noc, const float* cache_mask, const float* cache_img,
                                const float* cache_motion, const int* slot, const float* param, float* imgs_ot,
@@ -88,8 +91,10 @@ int usf_fakeobj_push_partials(int B, int H, int W);
  * raises USF_DEVERR_FAKEOBJ_BAD_SLOT. Two samples of one call must not name the
  * same slot. obj_mask: [B,1,H,W] dense; img: [B,3,H,W] dense; flow: [B,2,H,W]
  * with batch stride flow_bstride; slot: B int32 on the device; partials: caller
- * scratch of usf_fakeobj_push_partials(B,H,W) floats. The inputs must not alias
- * the cache. B <= 65535. */
+ * scratch of usf_fakeobj_push_partials(B,H,W) floats (no initialisation needed,
+ * scratch after return). The inputs must not alias the cache. B <= 65535.
+ * Alignment: obj_mask, img, partials 16 bytes; flow (a channel slice), slot and
+ * the cache tensors 4 bytes. */
 int usf_fakeobj_push_f32(const float* obj_mask, const float* img, const float* flow, long long flow_bstride,
                          const int* slot, float* cache_mask, float* cache_img, float* cache_motion, float* partials,
                          int B, int H, int W, int cache_size, void* stream);

@@ -134,7 +134,10 @@ long long usf_hg_workspace_bytes(int B, int H, int W, int K, int n_hyp);
  * B * USF_HG_SLOTS * USF_HG_RECORD_WORDS words, overwritten. workspace:
  * usf_hg_workspace_bytes bytes, 8-byte aligned, scratch of this call only.
  * K in [1, USF_HG_MAX_K], thr > 0, n_hyp in [1, USF_HG_MAX_HYP]. No host sync,
- * no float atomics; the records are bit-identical from call to call. */
+ * no float atomics; the records are bit-identical from call to call. workspace
+ * needs no initialisation.
+ * Alignment: flow 4 bytes (a channel slice); seg, occ 16 bytes; records 4
+ * bytes; workspace 8 bytes. A misaligned pointer is USF_EINVAL. */
 int usf_hg_fit_f32(const float* flow, long long flow_bstride, const float* seg, const float* occ, int K, float thr,
                    int n_hyp, unsigned long long seed, void* records, void* workspace, long long workspace_bytes,
                    int B, int H, int W, void* stream);
@@ -147,14 +150,17 @@ int usf_hg_loss_partials(int B, int H, int W);
  * H and p + flow are fp32 values, as the reference holds them; the per-pixel
  * arithmetic and the sums are fp64, combined in one fixed order.
  * H is a constant of the loss, as in the reference. partials: caller memory of
- * usf_hg_loss_partials doubles, 8-byte aligned. */
+ * usf_hg_loss_partials doubles, 8-byte aligned, no initialisation needed,
+ * scratch after return.
+ * Alignment: flow, records, out 4 bytes; seg 16 bytes; partials 8 bytes. */
 int usf_hg_loss_fwd_f32(const float* flow, long long flow_bstride, const float* seg, const void* records,
                         double* partials, float* out, int B, int H, int W, void* stream);
 
 /* grad_flow[b,c,p] = -sign(diff_c) * grad_loss[0] / (H * W * B) on the accepted
  * slots' segments, sign(0) = 0, and 0 elsewhere; diff is recomputed from flow,
  * seg and the records. grad_loss: one device float; grad_flow: [B,2,H,W]
- * dense, overwritten. */
+ * dense, overwritten.
+ * Alignment: flow, records, grad_loss 4 bytes; seg, grad_flow 16 bytes. */
 int usf_hg_loss_bwd_f32(const float* flow, long long flow_bstride, const float* seg, const void* records,
                         const float* grad_loss, float* grad_flow, int B, int H, int W, void* stream);
 

@@ -53,7 +53,9 @@ long long usf_segpool_state_words(int B, int C, int K);
  * usf_segpool_state_words(B,C,K) words, 4-byte aligned, written here and read by
  * the backward. Deterministic: the tables are merged with integer atomics (max
  * of order-preserving keys, counts) only. NaNs in proj are not supported.
- * B, C <= 65535. */
+ * B, C <= 65535. state needs no initialisation: the call initialises it.
+ * Alignment: proj, seg, spread 16 bytes; state 4 bytes. A misaligned pointer
+ * is USF_EINVAL. */
 int usf_segpool_fwd_f32(const float* proj, const float* seg, float* spread, void* state, int B, int C,
                         int H, int W, int K, void* stream);
 
@@ -66,7 +68,8 @@ int usf_segpool_fwd_f32(const float* proj, const float* seg, float* spread, void
  * proj, seg and state as the forward saw / left them; grad_spread, grad_proj:
  * [B,C,H,W] dense, grad_proj overwritten. Deterministic: G is summed in one
  * fixed order (row order within a wave step, steps and waves in sequence), no
- * float atomics. */
+ * float atomics.
+ * Alignment: proj, seg, grad_spread, grad_proj 16 bytes; state 4 bytes. */
 int usf_segpool_bwd_f32(const float* proj, const float* seg, const void* state, const float* grad_spread,
                         float* grad_proj, int B, int C, int H, int W, int K, void* stream);
 

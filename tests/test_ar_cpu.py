@@ -113,6 +113,10 @@ def _bwd(L, pred=1, target=1, ts=(24, 12, 4), noc=1, ns=(12, 4), coef=1, gl=1, g
     return L.usf_ar_loss_bwd_f32(pred, target, *ts, noc, *ns, coef, gl, gp, B, H, W, eps, q, None)
 
 
+# every pointer of _tf on a 16-byte boundary: the base of the alignment cases
+_TF16 = dict(img1=16, img2=16, flow=16, mask=16, theta=16, o1=16, o2=16, of=16, om=16)
+
+
 @pytest.mark.parametrize(
     "call,needle",
     [
@@ -146,6 +150,18 @@ def _bwd(L, pred=1, target=1, ts=(24, 12, 4), noc=1, ns=(12, 4), coef=1, gl=1, g
         (lambda L: _bwd(L, W=1), "H, W >= 2"),
         (lambda L: _bwd(L, B=0), "non-positive"),
         (lambda L: _bwd(L, q=0.0), "q=0"),
+        # the alignment contract (include/unsamflow_hip_ar.h): 20 where 16 bytes are required, 18 where 4
+        (lambda L: _tf(L, **{**_TF16, "img2": 20}), "img2 must be 16-byte aligned"),
+        (lambda L: _tf(L, **{**_TF16, "flow": 18}), "flow must be 4-byte aligned"),
+        (lambda L: _tf(L, **{**_TF16, "theta": 18}), "theta must be 4-byte aligned"),
+        (lambda L: _tf(L, **{**_TF16, "of": 24}), "flow_t must be 16-byte aligned"),
+        (lambda L: _fwd(L, pred=18, target=16, noc=16, part=16, out=16), "pred must be 4-byte aligned"),
+        (lambda L: _fwd(L, pred=20, target=18, noc=16, part=16, out=16), "target must be 4-byte aligned"),
+        (lambda L: _fwd(L, pred=16, target=16, noc=16, part=20, out=16), "partials must be 16-byte aligned"),
+        (lambda L: _fwd(L, pred=16, target=16, noc=16, part=16, out=18), "out must be 4-byte aligned"),
+        (lambda L: _bwd(L, pred=16, target=16, noc=18, coef=16, gl=16, gp=16), "noc must be 4-byte aligned"),
+        (lambda L: _bwd(L, pred=16, target=16, noc=16, coef=18, gl=16, gp=16), "coef must be 4-byte aligned"),
+        (lambda L: _bwd(L, pred=20, target=20, noc=20, coef=20, gl=20, gp=20), "grad_pred must be 16-byte aligned"),
     ],
 )
 def test_invalid_arguments_rejected_without_launch(lib, call, needle):

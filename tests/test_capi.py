@@ -84,6 +84,109 @@ def test_no_torch_types_in_abi():
         assert bad not in code
 
 
+def _arr(ctype, values):
+    return (ctype * len(values))(*values)
+
+
+def _misaligned(fn, args, index, value, name, align=None):
+    """One rejection case: ``args`` (every pointer 16-byte aligned, so the call
+    passes every other check) with argument ``index`` replaced by the fake
+    pointer ``value``; a (level, pointer) pair replaces one entry of a host
+    array. The message must name the parameter and its alignment."""
+    align = align or (4 if value % 4 else 16)
+
+    def call(L):
+        a = list(args)
+        if isinstance(value, tuple):
+            ptrs = [16] * len(a[index])
+            ptrs[value[0]] = value[1]
+            a[index] = _arr(ctypes.c_void_p, ptrs)
+        else:
+            a[index] = value
+        return getattr(L, fn)(*a)
+
+    return call, f"{fn}: {name} must be {align}-byte aligned"
+
+
+_P2 = _arr(ctypes.c_void_p, [16, 16])  # two levels / scales of fake pointers
+_HW2 = _arr(ctypes.c_int, [4, 4])
+_FBS2 = _arr(ctypes.c_longlong, [64, 64])
+_CORR_EX = (16, 16, 16, 81 * 16, 0, 0.1, None, None, 0, 1, 4, 4, 4, 4, None)
+_CORR_EX_ODD = (16, 16, 16, 81 * 25, 0, 0.1, None, None, 0, 1, 4, 5, 5, 4, None)
+_CORR_BWD_EX = (16, 16, 16, 81 * 16, None, None, 0.1, None, 16, 16, 1, 4, 4, 4, 4, None)
+_CORR_BWD_EX_ODD = (16, 16, 16, 81 * 25, None, None, 0.1, None, 16, 16, 1, 4, 5, 5, 4, None)
+_WARP_BWD = (16, 16, 32, 16, 16, 16, 1, 3, 4, 4, 1, None)
+_WARP_BWD_WS = (16, 16, 32, 16, 16, 16, 16, 1 << 40, 1, 3, 4, 4, 1, None)
+_PHOTO = (16, 16, 16, 16, 32, 16, 16, None, 1, 3, 4, 4, 1, 0.15, 0.85, None)
+_PHOTO_PAIR = (16, 16, 16, 16, 16, 64, 16, 16, None, 1, 3, 4, 4, 1, 0.15, 0.85, None)
+_PHOTO_PYR = (2, _P2, _P2, _P2, _P2, _P2, _FBS2, _HW2, _HW2, 16, 1 << 20, 16, None, 1, 3, 1, 0.15, 0.85, None)
+_PHOTO_PYR_BWD = (2, _P2, 16, 16, _P2, _HW2, _HW2, 1, None)
+_CONVEX_PYR = (2, _P2, _P2, _P2, _HW2, _HW2, 1, 4, 0.25, None)
+_CONVEX_PYR_BWD = (2, _P2, _P2, _P2, _P2, _P2, 16, 1 << 30, _HW2, _HW2, 1, 4, 0.25, None)
+
+# the alignment contract of include/unsamflow_hip.h, one or more pointers per launching entry
+# point: 20 where 16 bytes are required, 18 where 4 are (a slice); nothing is launched
+_ALIGNMENT_CASES = [
+    _misaligned("usf_corr_fwd_f32", (16, 16, 16, 1, 4, 4, 4, 4, None), 0, 20, "x1"),
+    _misaligned("usf_corr_fwd_f32", (16, 16, 16, 1, 4, 4, 4, 4, None), 2, 20, "out"),
+    _misaligned("usf_corr_bwd_f32", (16, 16, 16, 16, 16, 1, 4, 4, 4, 4, None), 2, 20, "gout"),
+    _misaligned("usf_corr_bwd_f32", (16, 16, 16, 16, 16, 1, 4, 4, 4, 4, None), 4, 24, "gx2"),
+    _misaligned("usf_corr_fwd_ex_f32", _CORR_EX, 1, 20, "x2"),
+    _misaligned("usf_corr_fwd_ex_f32", _CORR_EX, 2, 20, "out"),  # H*W % 4 == 0: a slice is 16-byte aligned
+    _misaligned("usf_corr_fwd_ex_f32", _CORR_EX_ODD, 2, 18, "out"),  # H*W = 25: 4 bytes are enough ...
+    _misaligned("usf_corr_fwd_ex_f32", _CORR_EX, 7, 24, "workspace"),
+    _misaligned("usf_corr_bwd_ex_f32", _CORR_BWD_EX, 2, 20, "gout"),
+    _misaligned("usf_corr_bwd_ex_f32", _CORR_BWD_EX_ODD, 2, 18, "gout"),
+    _misaligned("usf_corr_bwd_ex_f32", _CORR_BWD_EX, 5, 20, "act_mask"),
+    _misaligned("usf_corr_bwd_ex_f32", _CORR_BWD_EX, 8, 20, "gx1"),
+    _misaligned("usf_warp_fwd_f32", (16, 16, 32, 16, 1, 3, 4, 4, 1, None), 0, 20, "x"),
+    _misaligned("usf_warp_fwd_f32", (16, 16, 32, 16, 1, 3, 4, 4, 1, None), 1, 18, "flow"),
+    _misaligned("usf_warp_fwd_up_f32", (16, 16, 16, 16, 1, 3, 4, 4, 1, None), 1, 20, "coarse_flow"),
+    _misaligned("usf_warp_fwd_up_f32", (16, 16, 16, 16, 1, 3, 4, 4, 1, None), 2, 20, "up_flow"),
+    _misaligned("usf_warp_bwd_f32", _WARP_BWD, 3, 20, "gout"),
+    _misaligned("usf_warp_bwd_f32", _WARP_BWD, 1, 18, "flow"),
+    _misaligned("usf_warp_bwd_ex_f32", _WARP_BWD_WS, 4, 20, "gx"),
+    _misaligned("usf_warp_bwd_ex_f32", _WARP_BWD_WS, 1, 18, "flow"),
+    _misaligned("usf_warp_bwd_persist_f32", _WARP_BWD_WS, 5, 20, "gflow"),
+    _misaligned("usf_warp_bwd_persist_f32", _WARP_BWD_WS, 1, 18, "flow"),
+    _misaligned("usf_splat_map_f32", (16, 32, 16, 1, 4, 4, 0, None), 2, 20, "map"),
+    _misaligned("usf_splat_map_f32", (16, 32, 16, 1, 4, 4, 0, None), 0, 18, "flow"),
+    _misaligned("usf_occ_backward_f32", (16, 32, 16, 1, 4, 4, 0.2, None), 2, 20, "occ"),
+    _misaligned("usf_occ_backward_f32", (16, 32, 16, 1, 4, 4, 0.2, None), 0, 18, "flow21"),
+    _misaligned("usf_occ_backward_persist_f32", (16, 32, 16, 32, 64, 1, 4, 4, 0.2, None), 3, 20, "map"),
+    _misaligned("usf_occ_backward_persist_f32", (16, 32, 16, 32, 64, 1, 4, 4, 0.2, None), 0, 18, "flow21"),
+    _misaligned("usf_occ_vis_pair_persist_f32", (16, 64, 16, 32, 1 << 20, 1, 4, 4, 0.2, None), 2, 20, "vis"),
+    _misaligned("usf_occ_vis_pair_persist_f32", (16, 64, 16, 32, 1 << 20, 1, 4, 4, 0.2, None), 0, 18, "flow4"),
+    _misaligned("usf_occ_bidirection_f32", (16, 32, 16, 32, 16, 1, 4, 4, 0.01, 0.5, None), 4, 20, "occ"),
+    _misaligned("usf_occ_bidirection_f32", (16, 32, 16, 32, 16, 1, 4, 4, 0.01, 0.5, None), 2, 18, "flow21"),
+    _misaligned("usf_photo_loss_fwd_f32", _PHOTO, 1, 20, "tgt"),
+    _misaligned("usf_photo_loss_fwd_f32", _PHOTO, 3, 18, "flow"),
+    _misaligned("usf_photo_loss_fwd_f32", _PHOTO, 6, 18, "out"),
+    _misaligned("usf_photo_loss_fwd_f32", _PHOTO, 7, 20, "grad_basis"),
+    _misaligned("usf_photo_loss_pair_fwd_f32", _PHOTO_PAIR, 3, 20, "mask2"),
+    _misaligned("usf_photo_loss_pair_fwd_f32", _PHOTO_PAIR, 6, 24, "partials"),
+    _misaligned("usf_photo_loss_pyramid_fwd_f32", _PHOTO_PYR, 2, (1, 20), "im2", 16),
+    _misaligned("usf_photo_loss_pyramid_fwd_f32", _PHOTO_PYR, 5, (1, 18), "flow", 4),
+    _misaligned("usf_photo_loss_pyramid_bwd_f32", _PHOTO_PYR_BWD, 4, (1, 20), "grad_flow", 16),
+    _misaligned("usf_photo_loss_pyramid_bwd_f32", _PHOTO_PYR_BWD, 2, 18, "coef"),
+    _misaligned("usf_photo_loss_bwd_f32", (16, 16, 16, 16, 1, 4, 4, 1, None), 0, 20, "grad_basis"),
+    _misaligned("usf_photo_loss_bwd_f32", (16, 16, 16, 16, 1, 4, 4, 1, None), 2, 18, "grad_loss"),
+    _misaligned("usf_flow_upsample_f32", (16, 16, 1, 2, 4, 4, 2, None), 1, 20, "out"),
+    _misaligned("usf_flow_upsample_bwd_f32", (16, 16, 1, 2, 4, 4, 2, None), 0, 20, "grad_out"),
+    _misaligned("usf_flow_upsample_bwd_sum_f32", (16, 16, 16, 1, 2, 4, 4, 2, None), 1, 20, "grad_b"),
+    _misaligned("usf_convex_upsample_f32", (16, 16, 16, 1, 4, 4, 4, 0.25, None), 1, 20, "mask"),
+    _misaligned("usf_convex_upsample_f32", (16, 16, 16, 1, 4, 4, 2, 0.25, None), 2, 24, "out"),
+    _misaligned("usf_convex_upsample_bwd_f32", (16, 16, 16, 16, 16, 16, 1, 4, 4, 4, 0.25, None), 5, 20, "scratch"),
+    _misaligned("usf_convex_upsample_bwd_f32", (16, 16, 16, 16, 16, 16, 1, 4, 4, 4, 0.25, None), 2, 20, "grad_out"),
+    _misaligned("usf_convex_upsample_pyramid_f32", _CONVEX_PYR, 3, (0, 20), "out", 16),
+    _misaligned("usf_convex_upsample_pyramid_bwd_f32", _CONVEX_PYR_BWD, 5, (1, 20), "grad_mask", 16),
+    _misaligned("usf_convex_upsample_pyramid_bwd_f32", _CONVEX_PYR_BWD, 6, 24, "scratch"),
+    _misaligned("usf_area_pyramid_f32", (16, 16, 16, 16, 1, 3, 8, 8, None), 2, 20, "out2"),
+    _misaligned("usf_area_pyramid_f32", (16, 16, 16, 16, 1, 3, 8, 8, None), 0, 24, "x"),
+    (lambda L: L.usf_stream_copy_f32(20, 16, 16, None), "16-byte aligned pointers"),
+]
+
+
 @pytest.mark.parametrize(
     "call,needle",
     [
@@ -140,7 +243,7 @@ def test_no_torch_types_in_abi():
         (lambda L: L.usf_convex_upsample_bwd_f32(1, 1, 1, 1, 1, None, 2, 4, 4, 4, 0.25, None), "needs scratch"),
         (lambda L: L.usf_convex_upsample_bwd_f32(1, 1, None, 1, 1, 1, 2, 4, 4, 4, 0.25, None), "null input"),
         (lambda L: L.usf_photo_loss_pair_fwd_f32(1, 1, 1, None, 1, 64, 1, 1, None, 2, 3, 4, 4, 1, 0.15, 0.85, None), "null input"),
-    ],
+    ] + _ALIGNMENT_CASES,
 )
 def test_invalid_arguments_rejected_without_launch(lib, call, needle):
     rc = call(lib)
@@ -153,7 +256,7 @@ def test_error_string_cleared_on_next_call(lib):
     assert lib.usf_corr_fwd_f32(1, 1, 1, 0, 4, 4, 4, 4, None) == -1
     assert lib.usf_last_error_string() != b""
     # a warp bwd with neither output requested is a valid no-op (no launch)
-    assert lib.usf_warp_bwd_f32(1, 1, 32, 1, None, None, 1, 3, 4, 4, 1, None) == 0
+    assert lib.usf_warp_bwd_f32(16, 16, 32, 16, None, None, 1, 3, 4, 4, 1, None) == 0
     assert lib.usf_last_error_string() == b""
 
 

@@ -104,22 +104,35 @@ def _pair(L, im1=1, im2=1, m1=1, m2=1, flow=1, fbs=64, part=1, out=1, basis=None
     return L.usf_census_loss_pair_fwd_f32(im1, im2, m1, m2, flow, fbs, part, out, basis, B, C, H, W, pad, 1.0, None)
 
 
-def _pyr(L, n, B=1, C=3, pad=1, H=4, W=4, part=1, nfloats=1 << 20, out=1, im1=True):
+# every pointer of _fwd on a 16-byte boundary: the base of the alignment cases
+_AL = dict(src=16, tgt=16, mask=16, flow=16, part=16, out=16)
+
+
+def _pyr(L, n, B=1, C=3, pad=1, H=4, W=4, part=1, nfloats=1 << 20, out=1, im1=True, ptr=1, bad=None):
+    """``ptr``: the fake device pointer of every scale; ``bad``: im2 of scale 1 instead."""
     import ctypes
 
-    ptrs = (ctypes.c_void_p * 4)(1, 1, 1, 1)
+    ptrs = (ctypes.c_void_p * 4)(ptr, ptr, ptr, ptr)
+    if bad is not None:
+        return L.usf_census_loss_pyramid_fwd_f32(n, ptrs, (ctypes.c_void_p * 4)(ptr, bad, ptr, ptr), ptrs, ptrs, ptrs,
+                                                 (ctypes.c_longlong * 4)(*[4 * H * W] * 4), (ctypes.c_int * 4)(*[H] * 4),
+                                                 (ctypes.c_int * 4)(*[W] * 4), part, nfloats, out, None, B, C, pad, 1.0,
+                                                 None)
     Hs, Ws = (ctypes.c_int * 4)(H, H, H, H), (ctypes.c_int * 4)(W, W, W, W)
     fbs = (ctypes.c_longlong * 4)(*[4 * H * W] * 4)
     return L.usf_census_loss_pyramid_fwd_f32(n, ptrs if im1 else None, ptrs, ptrs, ptrs, ptrs, fbs, Hs, Ws, part,
                                              nfloats, out, None, B, C, pad, 1.0, None)
 
 
-def _pyr_bwd(L, n, basis=True):
+def _pyr_bwd(L, n, basis=True, ptr=1, coef=None, bad=None):
+    """``ptr``: every fake device pointer; ``coef``: its own; ``bad``: grad_flow of scale 1 instead."""
     import ctypes
 
-    ptrs = (ctypes.c_void_p * 4)(1, 1, 1, 1)
+    ptrs = (ctypes.c_void_p * 4)(ptr, ptr, ptr, ptr)
+    gflow = ptrs if bad is None else (ctypes.c_void_p * 4)(ptr, bad, ptr, ptr)
     hw = (ctypes.c_int * 4)(4, 4, 4, 4)
-    return L.usf_census_loss_pyramid_bwd_f32(n, ptrs if basis else None, 1, 1, ptrs, hw, hw, 1, None)
+    return L.usf_census_loss_pyramid_bwd_f32(n, ptrs if basis else None, ptr if coef is None else coef, ptr, gflow, hw,
+                                             hw, 1, None)
 
 
 @pytest.mark.parametrize(
@@ -159,6 +172,22 @@ def _pyr_bwd(L, n, basis=True):
         (lambda L: _pyr_bwd(L, 0), "nscale 0"),
         (lambda L: _pyr_bwd(L, 5), "nscale 5"),
         (lambda L: _pyr_bwd(L, 2, basis=False), "null pointer"),
+        # the alignment contract (include/unsamflow_hip_census.h): 20 where 16 bytes are required, 18 where 4
+        (lambda L: _fwd(L, **{**_AL, "src": 20}), "src must be 16-byte aligned"),
+        (lambda L: _fwd(L, **{**_AL, "mask": 24}), "mask must be 16-byte aligned"),
+        (lambda L: _fwd(L, **{**_AL, "flow": 18}), "flow must be 4-byte aligned"),
+        (lambda L: _fwd(L, **{**_AL, "out": 18}), "out must be 4-byte aligned"),
+        (lambda L: _fwd(L, **{**_AL, "basis": 20}), "grad_basis must be 16-byte aligned"),
+        (lambda L: _pair(L, im1=16, im2=20, m1=16, m2=16, flow=16, part=16, out=16), "im2 must be 16-byte aligned"),
+        (lambda L: _pair(L, im1=16, im2=16, m1=16, m2=16, flow=18, part=16, out=16), "flow must be 4-byte aligned"),
+        (lambda L: _pair(L, im1=16, im2=16, m1=16, m2=16, flow=16, part=24, out=16), "partials must be 16-byte aligned"),
+        (lambda L: L.usf_census_loss_bwd_f32(20, 16, 16, 16, 1, 4, 4, 1, None), "grad_basis must be 16-byte aligned"),
+        (lambda L: L.usf_census_loss_bwd_f32(16, 18, 16, 16, 1, 4, 4, 1, None), "coef must be 4-byte aligned"),
+        (lambda L: L.usf_census_loss_bwd_f32(16, 16, 16, 24, 1, 4, 4, 2, None), "grad_flow must be 16-byte aligned"),
+        (lambda L: _pyr(L, 2, part=16, out=16, ptr=16, bad=20), "im2 must be 16-byte aligned"),
+        (lambda L: _pyr(L, 2, part=16, out=18, ptr=16), "out must be 4-byte aligned"),
+        (lambda L: _pyr_bwd(L, 2, ptr=16, bad=20), "grad_flow must be 16-byte aligned"),
+        (lambda L: _pyr_bwd(L, 2, ptr=16, coef=18), "coef must be 4-byte aligned"),
     ],
 )
 def test_invalid_arguments_rejected_without_launch(lib, call, needle):

@@ -122,6 +122,13 @@ def _bwd(L, go=4, gbs=24, y=16, gin=32, gb=4, ws=None, nws=0, B=1, C=2, H=3, W=4
         (lambda L: _bwd(L, B=16, C=16, H=128, W=416, gbs=16 * 128 * 416), "workspace of"),
         (lambda L: _bwd(L, B=16, C=16, H=128, W=416, gbs=16 * 128 * 416, ws=64, nws=16), "short"),
         (lambda L: _bwd(L, C=0), "non-positive"),
+        # the alignment contract (include/unsamflow_hip_convepi.h): 20 where 16 bytes are required, 18 where 4
+        (lambda L: _fwd(L, y=20), "y must be 16-byte"),
+        (lambda L: _fwd(L, bias=18), "bias 4-byte aligned"),
+        (lambda L: _bwd(L, go=18), "misaligned, or gout_bstride"),
+        (lambda L: _bwd(L, y=20), "16-byte aligned tensors"),
+        (lambda L: _bwd(L, gin=24), "16-byte aligned tensors"),
+        (lambda L: _bwd(L, gb=18), "misaligned, or workspace"),
     ],
 )
 def test_invalid_arguments_rejected_without_launch(lib, call, needle):

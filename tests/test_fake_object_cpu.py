@@ -275,6 +275,11 @@ def _paste(L, img1=1, img2=1, flow=1, fbs=24, noc=1, cm=1, ci=1, cmo=1, slot=1, 
                                         size, y0, x0, ch, cw, None)
 
 
+# every pointer on a 16-byte boundary: the base of the alignment cases
+_PASTE16 = dict(img1=16, img2=16, flow=16, noc=16, cm=16, ci=16, cmo=16, slot=16, param=16, o1=16, of=16, on=16)
+_PUSH16 = dict(mask=16, img=16, flow=16, slot=16, cm=16, ci=16, cmo=16, part=16)
+
+
 def _push(L, mask=1, img=1, flow=1, fbs=24, slot=1, cm=1, ci=1, cmo=1, part=1, B=1, H=3, W=4, size=4):
     return L.usf_fakeobj_push_f32(mask, img, flow, fbs, slot, cm, ci, cmo, part, B, H, W, size, None)
 
@@ -310,6 +315,18 @@ def _push(L, mask=1, img=1, flow=1, fbs=24, slot=1, cm=1, ci=1, cmo=1, part=1, B
         (lambda L: _push(L, B=0), "non-positive"),
         (lambda L: _push(L, size=-2), "cache_size=-2"),
         (lambda L: _push(L, B=70000), "B=70000"),
+        # the alignment contract (include/unsamflow_hip_fakeobj.h): 20 where 16 bytes are required, 18 where 4
+        (lambda L: _paste(L, **{**_PASTE16, "img2": 20}), "img2 must be 16-byte aligned"),
+        (lambda L: _paste(L, **{**_PASTE16, "ci": 18}), "cache_img must be 4-byte aligned"),
+        (lambda L: _paste(L, **{**_PASTE16, "flow": 18}), "flow must be 4-byte aligned"),
+        (lambda L: _paste(L, **{**_PASTE16, "cmo": 18}), "cache_motion must be 4-byte aligned"),
+        (lambda L: _paste(L, **{**_PASTE16, "param": 18}), "param must be 4-byte aligned"),
+        (lambda L: _paste(L, **{**_PASTE16, "on": 20}), "noc_ot must be 16-byte aligned"),
+        (lambda L: _push(L, **{**_PUSH16, "mask": 20}), "obj_mask must be 16-byte aligned"),
+        (lambda L: _push(L, **{**_PUSH16, "cm": 18}), "cache_mask must be 4-byte aligned"),
+        (lambda L: _push(L, **{**_PUSH16, "slot": 18}), "slot must be 4-byte aligned"),
+        (lambda L: _push(L, **{**_PUSH16, "flow": 18}), "flow must be 4-byte aligned"),
+        (lambda L: _push(L, **{**_PUSH16, "part": 24}), "partials must be 16-byte aligned"),
     ],
 )
 def test_invalid_arguments_rejected_without_launch(lib, call, needle):

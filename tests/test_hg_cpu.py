@@ -247,6 +247,11 @@ def _fit(L, flow=8, fbs=24, seg=8, occ=8, K=5, thr=0.5, n_hyp=16, rec=8, ws=8, w
     (dict(seg=None), "null input"), (dict(occ=None), "null input"), (dict(rec=None), "null output"),
     (dict(ws=None), "null output"), (dict(wsb=16), "workspace"), (dict(fbs=23), "flow_bstride"),
     (dict(B=0), "shape"), (dict(ws=12), "aligned"),
+    # the alignment contract (include/unsamflow_hip_hg.h): 20 where 16 bytes are required, 18 where 4
+    (dict(flow=16, seg=20, occ=16, rec=16, ws=16), "seg must be 16-byte aligned"),
+    (dict(flow=16, seg=16, occ=24, rec=16, ws=16), "occ must be 16-byte aligned"),
+    (dict(flow=18, seg=16, occ=16, rec=16, ws=16), "flow must be 4-byte aligned"),
+    (dict(flow=16, seg=16, occ=16, rec=18, ws=16), "records not 4-byte"),
 ])
 def test_fit_rejects_bad_arguments_before_the_device(lib, kw, what):
     assert _fit(lib, **kw) == EINVAL
@@ -266,6 +271,18 @@ def test_loss_entries_reject_bad_arguments_before_the_device(lib):
         assert fn(fbs=5) == EINVAL and "flow_bstride" in lib.usf_last_error_string().decode()
         assert fn(H=0) == EINVAL
     assert bwd(g=None) == EINVAL and "null input" in lib.usf_last_error_string().decode()
+    # the alignment contract: 20 where 16 bytes are required, 18 where 4 are
+    al = dict(flow=16, seg=16, rec=16)
+    for call, kw, what in ((fwd, dict(seg=20), "seg must be 16-byte aligned"),
+                           (fwd, dict(flow=18), "flow must be 4-byte aligned"),
+                           (fwd, dict(out=18), "out must be 4-byte aligned"),
+                           (fwd, dict(part=20), "partials not 8-byte aligned"),
+                           (bwd, dict(seg=24), "seg must be 16-byte aligned"),
+                           (bwd, dict(g=18), "grad_loss must be 4-byte aligned"),
+                           (bwd, dict(gf=20), "grad_flow must be 16-byte aligned")):
+        base = {**al, **(dict(part=16, out=16) if call is fwd else dict(g=16, gf=16))}
+        assert call(**{**base, **kw}) == EINVAL
+        assert what in lib.usf_last_error_string().decode(), (kw, lib.usf_last_error_string())
 
 
 def test_hg_kernels_do_not_spill():

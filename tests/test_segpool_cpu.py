@@ -206,6 +206,13 @@ def _bwd(L, proj=4, seg=4, state=4, gs=4, gp=4, B=1, C=2, H=3, W=4, K=5):
         (lambda L: _bwd(L, gp=None), "null output"),
         (lambda L: _bwd(L, H=0), "non-positive"),
         (lambda L: _bwd(L, W=0), "non-positive"),
+        # the alignment contract (include/unsamflow_hip_segpool.h): 20 where 16 bytes are required, 18 where 4
+        (lambda L: _fwd(L, proj=20, seg=16, spread=16, state=16), "proj must be 16-byte aligned"),
+        (lambda L: _fwd(L, proj=16, seg=16, spread=24, state=16), "spread must be 16-byte aligned"),
+        (lambda L: _fwd(L, proj=16, seg=16, spread=16, state=18), "state not 4-byte aligned"),
+        (lambda L: _bwd(L, proj=16, seg=20, state=16, gs=16, gp=16), "seg must be 16-byte aligned"),
+        (lambda L: _bwd(L, proj=16, seg=16, state=16, gs=16, gp=20), "grad_proj must be 16-byte aligned"),
+        (lambda L: _bwd(L, proj=16, seg=16, state=18, gs=16, gp=16), "state not 4-byte aligned"),
     ],
 )
 def test_invalid_arguments_rejected_without_launch(lib, call, needle):

@@ -8,6 +8,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
 
 #include "../../include/unsamflow_hip.h"
 #include "../../include/unsamflow_hip_ar.h"
@@ -46,6 +47,39 @@ static bool check_dims(const char* fn, int B, int C, int H, int W) {
   }
   return true;
 }
+
+// The alignment contract of the headers: {parameter name, pointer, required
+// alignment in bytes}. The kernels choose their 8- and 16-byte paths from the
+// shape, so the address must hold what the shape promises; this runs after the
+// other argument checks and before any launch. A null pointer passes (whether
+// it may be null is checked before).
+struct PtrAlign {
+  const char* name;
+  const void* p;
+  unsigned align;
+};
+
+static bool check_align(const char* fn, std::initializer_list<PtrAlign> ps) {
+  for (const PtrAlign& a : ps)
+    if (a.p && (reinterpret_cast<uintptr_t>(a.p) & (a.align - 1u))) {
+      set_error("%s: %s must be %u-byte aligned", fn, a.name, a.align);
+      return false;
+    }
+  return true;
+}
+
+// check_align of the per-level (per-scale) pointers of a host array; nullable array
+static bool check_align_each(const char* fn, const char* name, const void* const* ps, int n, unsigned align) {
+  if (!ps) return true;
+  for (int k = 0; k < n; ++k)
+    if (!check_align(fn, {{name, ps[k], align}})) return false;
+  return true;
+}
+
+// A channel slice of a dense NCHW buffer starts c0 * H*W floats into it: it is
+// 16-byte aligned whenever H*W % 4 == 0, and only such shapes take a vector
+// path through a slice pointer. Any other shape needs 4 bytes.
+static unsigned slice_align(int H, int W) { return ((long long)H * W) % 4 == 0 ? 16u : 4u; }
 
 // USF_SYNC_CHECK=1: synchronise the stream after every launch and report any
 // asynchronous fault against the launch that caused it (debug only).
@@ -128,6 +162,7 @@ int usf_corr_fwd_f32(const float* x1, const float* x2, float* out, int B, int C,
     set_error("usf_corr_fwd_f32: null pointer");
     return USF_EINVAL;
   }
+  if (!check_align("usf_corr_fwd_f32", {{"x1", x1, 16}, {"x2", x2, 16}, {"out", out, 16}})) return USF_EINVAL;
   if (const int pe = pre_check("usf_corr_fwd_f32", (hipStream_t)stream)) return pe;
   const long long k2 = (long long)(2 * d + 1) * (2 * d + 1);
   return finish("usf_corr_fwd_f32",
@@ -172,6 +207,12 @@ int usf_corr_fwd_ex_f32(const float* x1, const float* x2, float* out, long long 
     set_error("usf_corr_fwd_ex_f32: act_mask needs act = LeakyReLU (act=%d)", act);
     return USF_EINVAL;
   }
+  if (!check_align("usf_corr_fwd_ex_f32", {{"x1", x1, 16},
+                                           {"x2", x2, 16},
+                                           {"out", out, slice_align(H, W)},
+                                           {"act_mask", act_mask, 16},
+                                           {"workspace", workspace, 16}}))
+    return USF_EINVAL;
   if (const int pe = pre_check("usf_corr_fwd_ex_f32", (hipStream_t)stream)) return pe;
   FwdEpi ep{out_bstride, act, slope};
   ep.mask = act_mask;
@@ -193,6 +234,8 @@ int usf_corr_bwd_f32(const float* x1, const float* x2, const float* gout, float*
     set_error("usf_corr_bwd_f32: null input pointer");
     return USF_EINVAL;
   }
+  if (!check_align("usf_corr_bwd_f32", {{"x1", x1, 16}, {"x2", x2, 16}, {"gout", gout, 16}, {"gx1", gx1, 16}, {"gx2", gx2, 16}}))
+    return USF_EINVAL;
   if (const int pe = pre_check("usf_corr_bwd_f32", (hipStream_t)stream)) return pe;
   const long long k2 = (long long)(2 * d + 1) * (2 * d + 1);
   return finish("usf_corr_bwd_f32",
@@ -220,7 +263,18 @@ int usf_corr_bwd_ex_f32(const float* x1, const float* x2, const float* gout, lon
     set_error("usf_corr_bwd_ex_f32: gradient batch stride %lld < (2d+1)^2*H*W", g_bstride);
     return USF_EINVAL;
   }
+  const auto aligned = [&] {
+    return check_align("usf_corr_bwd_ex_f32", {{"x1", x1, 16},
+                                               {"x2", x2, 16},
+                                               {"gout", gout, slice_align(H, W)},
+                                               {"act_out", act_mask ? nullptr : act_out, slice_align(H, W)},
+                                               {"act_mask", act_mask, 16},
+                                               {"scratch", act_mask || !act_out ? nullptr : scratch, 16},
+                                               {"gx1", gx1, 16},
+                                               {"gx2", gx2, 16}});
+  };
   if (act_mask) {  // derivative from the forward's sign mask, inside the backward's g loads
+    if (!aligned()) return USF_EINVAL;
     if (const int pe = pre_check("usf_corr_bwd_ex_f32", (hipStream_t)stream)) return pe;
     BwdEpi ep{g_bstride};
     ep.mask = act_mask;
@@ -233,6 +287,7 @@ int usf_corr_bwd_ex_f32(const float* x1, const float* x2, const float* gout, lon
     set_error("usf_corr_bwd_ex_f32: act_out needs a scratch of usf_corr_bwd_ex_scratch() floats here");
     return USF_EINVAL;
   }
+  if (!aligned()) return USF_EINVAL;
   if (const int pe = pre_check("usf_corr_bwd_ex_f32", (hipStream_t)stream)) return pe;
   const BwdEpi ep{g_bstride};
   if (act_out) {  // derivative + de-concat in one dense pass, then the plain backward
@@ -270,6 +325,7 @@ int usf_warp_fwd_f32(const float* x, const float* flow, long long flow_bstride, 
     set_error("usf_warp_fwd_f32: flow batch stride %lld < 2*H*W", flow_bstride);
     return USF_EINVAL;
   }
+  if (!check_align("usf_warp_fwd_f32", {{"x", x, 16}, {"flow", flow, 4}, {"out", out, 16}})) return USF_EINVAL;
   if (const int pe = pre_check("usf_warp_fwd_f32", (hipStream_t)stream)) return pe;
   return finish("usf_warp_fwd_f32",
                 warp_fwd_launch(x, flow, flow_bstride, out, B, C, H, W, pad_mode, (hipStream_t)stream),
@@ -293,6 +349,8 @@ int usf_warp_fwd_up_f32(const float* x, const float* coarse_flow, float* up_flow
     set_error("%s: null pointer", fn);
     return USF_EINVAL;
   }
+  if (!check_align(fn, {{"x", x, 16}, {"coarse_flow", coarse_flow, 16}, {"up_flow", up_flow, 16}, {"out", out, 16}}))
+    return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn, warp_fwd_up_launch(x, coarse_flow, up_flow, out, B, C, H, W, pad_mode, (hipStream_t)stream),
                 (hipStream_t)stream);
@@ -340,6 +398,8 @@ static int warp_bwd_common(const char* fn, const float* x, const float* flow, lo
       return USF_EINVAL;
     }
   }
+  if (!check_align(fn, {{"x", x, 16}, {"flow", flow, 4}, {"gout", gout, 16}, {"gx", gx, 16}, {"gflow", gflow, 16}}))
+    return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   hipError_t e = warp_bwd_launch(x, flow, flow_bstride, gout, gx, gflow, B, C, H, W, pad_mode, (hipStream_t)stream,
                                  ws, ws_bytes, persist);
@@ -397,6 +457,7 @@ int usf_splat_map_f32(const float* flow, long long flow_bstride, float* map, int
                       int absolute, void* stream) {
   clear_error();
   if (!check_splat("usf_splat_map_f32", flow, flow_bstride, map, B, H, W)) return USF_EINVAL;
+  if (!check_align("usf_splat_map_f32", {{"flow", flow, 4}, {"map", map, 16}})) return USF_EINVAL;
   if (const int pe = pre_check("usf_splat_map_f32", (hipStream_t)stream)) return pe;
   return finish("usf_splat_map_f32",
                 splat_launch(flow, flow_bstride, map, B, H, W, absolute != 0, (hipStream_t)stream),
@@ -407,6 +468,7 @@ int usf_occ_backward_f32(const float* flow21, long long flow_bstride, float* occ
                          int W, float th, void* stream) {
   clear_error();
   if (!check_splat("usf_occ_backward_f32", flow21, flow_bstride, occ, B, H, W)) return USF_EINVAL;
+  if (!check_align("usf_occ_backward_f32", {{"flow21", flow21, 4}, {"occ", occ, 16}})) return USF_EINVAL;
   if (const int pe = pre_check("usf_occ_backward_f32", (hipStream_t)stream)) return pe;
   return finish("usf_occ_backward_f32",
                 occ_backward_launch(flow21, flow_bstride, occ, B, H, W, th, (hipStream_t)stream),
@@ -423,6 +485,7 @@ int usf_occ_backward_persist_f32(const float* flow21, long long flow_bstride, fl
               map_bytes);
     return USF_EINVAL;
   }
+  if (!check_align(fn, {{"flow21", flow21, 4}, {"occ", occ, 16}, {"map", map, 16}})) return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   hipError_t e = occ_backward_persist_launch(flow21, flow_bstride, occ, map, B, H, W, th, (hipStream_t)stream);
   if (e == hipSuccess && sync_check_on((hipStream_t)stream))
@@ -452,6 +515,7 @@ int usf_occ_vis_pair_persist_f32(const float* flow4, long long flow_bstride, flo
     set_error("%s: 2*B*H*W beyond 32-bit indexing", fn);
     return USF_EINVAL;
   }
+  if (!check_align(fn, {{"flow4", flow4, 4}, {"vis", vis, 16}, {"map", map, 16}})) return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   hipError_t e = occ_vis_pair_persist_launch(flow4, vis, map, B, H, W, th, (hipStream_t)stream);
   if (e == hipSuccess && sync_check_on((hipStream_t)stream))
@@ -465,6 +529,8 @@ int usf_occ_bidirection_f32(const float* flow12, long long flow12_bstride, const
   clear_error();
   if (!check_splat("usf_occ_bidirection_f32", flow12, flow12_bstride, occ, B, H, W) ||
       !check_splat("usf_occ_bidirection_f32", flow21, flow21_bstride, occ, B, H, W))
+    return USF_EINVAL;
+  if (!check_align("usf_occ_bidirection_f32", {{"flow12", flow12, 4}, {"flow21", flow21, 4}, {"occ", occ, 16}}))
     return USF_EINVAL;
   if (const int pe = pre_check("usf_occ_bidirection_f32", (hipStream_t)stream)) return pe;
   return finish("usf_occ_bidirection_f32",
@@ -525,6 +591,20 @@ static bool check_loss_outputs(const char* fn, const float* partials, const floa
   return partials && out;
 }
 
+// alignment of one scale's pointers (pair: the names of the with_bk forms)
+static bool check_loss_align(const char* fn, bool pair, const float* a, const float* b, const float* m1,
+                             const float* m2, const float* flow, const float* partials, const float* out,
+                             const float* basis) {
+  return check_align(fn, {{pair ? "im1" : "src", a, 16},
+                          {pair ? "im2" : "tgt", b, 16},
+                          {pair ? "mask1" : "mask", m1, 16},
+                          {"mask2", m2, 16},
+                          {"flow", flow, 4},
+                          {"partials", partials, 16},
+                          {"out", out, 4},
+                          {"grad_basis", basis, 16}});
+}
+
 static long long loss_pyramid_partials(const LossKind& kind, int nscale, const int* H, const int* W, int B) {
   if (nscale < 1 || nscale > 4 || !H || !W || B <= 0) return 0;
   long long n = 0;
@@ -559,6 +639,10 @@ static bool check_loss_pyramid(const char* fn, const LossKind& kind, int nscale,
               kind.name, need);
     return false;
   }
+  for (int k = 0; k < nscale; ++k)
+    if (!check_loss_align(fn, true, im1[k], im2[k], mask1[k], mask2[k], flow[k], partials, out,
+                          grad_basis ? grad_basis[k] : nullptr))
+      return false;
   return true;
 }
 
@@ -586,6 +670,12 @@ static int loss_bwd(const char* fn, const LossKind& kind, int nscale, const floa
     set_error("%s: ndir=%d (1 or 2)", fn, ndir);
     return USF_EINVAL;
   }
+  for (int k = 0; k < nscale; ++k)
+    if (!check_align(fn, {{"grad_basis", grad_basis[k], 16},
+                          {"coef", coef, 4},
+                          {"grad_loss", grad_loss, 4},
+                          {"grad_flow", grad_flow[k], 16}}))
+      return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn, kind.bwd_launch(nscale, grad_basis, coef, grad_loss, grad_flow, H, W, B, ndir, (hipStream_t)stream),
                 (hipStream_t)stream);
@@ -602,7 +692,8 @@ int usf_photo_loss_fwd_f32(const float* src, const float* tgt, const float* mask
   clear_error();
   const char* fn = "usf_photo_loss_fwd_f32";
   if (!check_loss_inputs(fn, kPhoto, src, tgt, mask, mask, flow, flow_bstride, 2, B, C, H, W, pad_mode) ||
-      !check_loss_outputs(fn, partials, out))
+      !check_loss_outputs(fn, partials, out) ||
+      !check_loss_align(fn, false, src, tgt, mask, nullptr, flow, partials, out, grad_basis))
     return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn,
@@ -618,7 +709,8 @@ int usf_photo_loss_pair_fwd_f32(const float* im1, const float* im2, const float*
   clear_error();
   const char* fn = "usf_photo_loss_pair_fwd_f32";
   if (!check_loss_inputs(fn, kPhoto, im1, im2, mask1, mask2, flow, flow_bstride, 4, B, C, H, W, pad_mode) ||
-      !check_loss_outputs(fn, partials, out))
+      !check_loss_outputs(fn, partials, out) ||
+      !check_loss_align(fn, true, im1, im2, mask1, mask2, flow, partials, out, grad_basis))
     return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn,
@@ -674,7 +766,8 @@ int usf_census_loss_fwd_f32(const float* src, const float* tgt, const float* mas
   clear_error();
   const char* fn = "usf_census_loss_fwd_f32";
   if (!check_loss_inputs(fn, kCensus, src, tgt, mask, mask, flow, flow_bstride, 2, B, C, H, W, pad_mode) ||
-      !check_loss_outputs(fn, partials, out))
+      !check_loss_outputs(fn, partials, out) ||
+      !check_loss_align(fn, false, src, tgt, mask, nullptr, flow, partials, out, grad_basis))
     return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn,
@@ -690,7 +783,8 @@ int usf_census_loss_pair_fwd_f32(const float* im1, const float* im2, const float
   clear_error();
   const char* fn = "usf_census_loss_pair_fwd_f32";
   if (!check_loss_inputs(fn, kCensus, im1, im2, mask1, mask2, flow, flow_bstride, 4, B, C, H, W, pad_mode) ||
-      !check_loss_outputs(fn, partials, out))
+      !check_loss_outputs(fn, partials, out) ||
+      !check_loss_align(fn, true, im1, im2, mask1, mask2, flow, partials, out, grad_basis))
     return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn,
@@ -769,6 +863,10 @@ int usf_ar_transform_f32(const float* img1, const float* img2, const float* flow
     set_error("%s: flow batch stride %lld < 2*H*W", fn, flow_bstride);
     return USF_EINVAL;
   }
+  if (!check_align(fn, {{"img1", img1, 16},     {"img2", img2, 16},     {"flow", flow, 4},      {"mask", mask, 16},
+                        {"theta", theta, 4},    {"noise1", noise1, 16}, {"noise2", noise2, 16}, {"img1_t", img1_t, 16},
+                        {"img2_t", img2_t, 16}, {"flow_t", flow_t, 16}, {"mask_t", mask_t, 16}}))
+    return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn,
                 ar_transform_launch(img1, img2, flow, flow_bstride, mask, theta, noise1, noise2, img1_t, img2_t,
@@ -814,6 +912,9 @@ int usf_ar_loss_fwd_f32(const float* pred, const float* target, long long target
     set_error("%s: null output pointer", fn);
     return USF_EINVAL;
   }
+  if (!check_align(fn, {{"pred", pred, 4}, {"target", target, 4}, {"noc", noc, 4}, {"denom", denom, 4},
+                        {"partials", partials, 16}, {"out", out, 4}}))
+    return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn,
                 ar_loss_fwd_launch(pred, target, target_bstride, target_cstride, target_rstride, noc, noc_bstride,
@@ -838,6 +939,9 @@ int usf_ar_loss_bwd_f32(const float* pred, const float* target, long long target
     set_error("%s: null output pointer", fn);
     return USF_EINVAL;
   }
+  if (!check_align(fn, {{"pred", pred, 4}, {"target", target, 4}, {"noc", noc, 4}, {"coef", coef, 4},
+                        {"grad_loss", grad_loss, 4}, {"grad_pred", grad_pred, 16}}))
+    return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn,
                 ar_loss_bwd_launch(pred, target, target_bstride, target_cstride, target_rstride, noc, noc_bstride,
@@ -890,6 +994,19 @@ int usf_fakeobj_paste_crop_f32(const float* img1, const float* img2, const float
     set_error("%s: null output pointer", fn);
     return USF_EINVAL;
   }
+  if (!check_align(fn, {{"img1", img1, 16},
+                        {"img2", img2, 16},
+                        {"flow", flow, 4},
+                        {"noc", noc, 16},
+                        {"cache_mask", cache_mask, 4},
+                        {"cache_img", cache_img, 4},
+                        {"cache_motion", cache_motion, 4},
+                        {"slot", slot, 4},
+                        {"param", param, 4},
+                        {"imgs_ot", imgs_ot, 16},
+                        {"flow_ot", flow_ot, 16},
+                        {"noc_ot", noc_ot, 16}}))
+    return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn,
                 fakeobj_paste_crop_launch(img1, img2, flow, flow_bstride, noc, cache_mask, cache_img, cache_motion, slot,
@@ -916,6 +1033,15 @@ int usf_fakeobj_push_f32(const float* obj_mask, const float* img, const float* f
     set_error("%s: null output pointer", fn);
     return USF_EINVAL;
   }
+  if (!check_align(fn, {{"obj_mask", obj_mask, 16},
+                        {"img", img, 16},
+                        {"flow", flow, 4},
+                        {"slot", slot, 4},
+                        {"cache_mask", cache_mask, 4},
+                        {"cache_img", cache_img, 4},
+                        {"cache_motion", cache_motion, 4},
+                        {"partials", partials, 16}}))
+    return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn,
                 fakeobj_push_launch(obj_mask, img, flow, flow_bstride, slot, cache_mask, cache_img, cache_motion,
@@ -960,6 +1086,7 @@ int usf_segpool_fwd_f32(const float* proj, const float* seg, float* spread, void
     set_error("%s: state not 4-byte aligned", fn);
     return USF_EINVAL;
   }
+  if (!check_align(fn, {{"proj", proj, 16}, {"seg", seg, 16}, {"spread", spread, 16}})) return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn,
                 segpool_fwd_launch(proj, seg, spread, static_cast<unsigned*>(state), B, C, H, W, K,
@@ -984,6 +1111,8 @@ int usf_segpool_bwd_f32(const float* proj, const float* seg, const void* state, 
     set_error("%s: state not 4-byte aligned", fn);
     return USF_EINVAL;
   }
+  if (!check_align(fn, {{"proj", proj, 16}, {"seg", seg, 16}, {"grad_spread", grad_spread, 16}, {"grad_proj", grad_proj, 16}}))
+    return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn,
                 segpool_bwd_launch(proj, seg, static_cast<const unsigned*>(state), grad_spread, grad_proj, B, C, H, W,
@@ -1054,6 +1183,7 @@ int usf_hg_fit_f32(const float* flow, long long flow_bstride, const float* seg, 
     set_error("%s: workspace of %lld bytes, need %lld (usf_hg_workspace_bytes)", fn, workspace_bytes, need);
     return USF_EINVAL;
   }
+  if (!check_align(fn, {{"flow", flow, 4}, {"seg", seg, 16}, {"occ", occ, 16}})) return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn,
                 hg_fit_launch(flow, flow_bstride, seg, occ, K, thr, n_hyp, seed, static_cast<int*>(records), workspace,
@@ -1083,6 +1213,7 @@ int usf_hg_loss_fwd_f32(const float* flow, long long flow_bstride, const float* 
     set_error("%s: records not 4-byte or partials not 8-byte aligned", fn);
     return USF_EINVAL;
   }
+  if (!check_align(fn, {{"flow", flow, 4}, {"seg", seg, 16}, {"out", out, 4}})) return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn,
                 hg_loss_fwd_launch(flow, flow_bstride, seg, static_cast<const int*>(records), partials, out, B, H, W,
@@ -1107,6 +1238,8 @@ int usf_hg_loss_bwd_f32(const float* flow, long long flow_bstride, const float* 
     set_error("%s: records not 4-byte aligned", fn);
     return USF_EINVAL;
   }
+  if (!check_align(fn, {{"flow", flow, 4}, {"seg", seg, 16}, {"grad_loss", grad_loss, 4}, {"grad_flow", grad_flow, 16}}))
+    return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn,
                 hg_loss_bwd_launch(flow, flow_bstride, seg, static_cast<const int*>(records), grad_loss, grad_flow, B,
@@ -1126,6 +1259,7 @@ int usf_flow_upsample_f32(const float* flow, float* out, int B, int C, int H, in
     set_error("usf_flow_upsample_f32: null pointer");
     return USF_EINVAL;
   }
+  if (!check_align("usf_flow_upsample_f32", {{"flow", flow, 16}, {"out", out, 16}})) return USF_EINVAL;
   if (const int pe = pre_check("usf_flow_upsample_f32", (hipStream_t)stream)) return pe;
   return finish("usf_flow_upsample_f32",
                 upsample_fwd_launch(flow, out, B, C, H, W, factor, (hipStream_t)stream),
@@ -1144,6 +1278,8 @@ int usf_flow_upsample_bwd_f32(const float* grad_out, float* grad_flow, int B, in
     set_error("usf_flow_upsample_bwd_f32: null pointer");
     return USF_EINVAL;
   }
+  if (!check_align("usf_flow_upsample_bwd_f32", {{"grad_out", grad_out, 16}, {"grad_flow", grad_flow, 16}}))
+    return USF_EINVAL;
   if (const int pe = pre_check("usf_flow_upsample_bwd_f32", (hipStream_t)stream)) return pe;
   return finish("usf_flow_upsample_bwd_f32",
                 upsample_bwd_launch(grad_out, grad_flow, B, C, H, W, factor, (hipStream_t)stream),
@@ -1163,6 +1299,7 @@ int usf_flow_upsample_bwd_sum_f32(const float* grad_a, const float* grad_b, floa
     set_error("%s: null pointer", fn);
     return USF_EINVAL;
   }
+  if (!check_align(fn, {{"grad_a", grad_a, 16}, {"grad_b", grad_b, 16}, {"grad_flow", grad_flow, 16}})) return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn, upsample_bwd_launch(grad_a, grad_flow, B, C, H, W, factor, (hipStream_t)stream, grad_b),
                 (hipStream_t)stream);
@@ -1190,6 +1327,7 @@ int usf_convex_upsample_f32(const float* flow, const float* mask, float* out, in
     set_error("%s: null pointer", fn);
     return USF_EINVAL;
   }
+  if (!check_align(fn, {{"flow", flow, 16}, {"mask", mask, 16}, {"out", out, 16}})) return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn, convex_fwd_launch(flow, mask, out, B, H, W, factor, mask_scale, (hipStream_t)stream),
                 (hipStream_t)stream);
@@ -1215,6 +1353,13 @@ int usf_convex_upsample_bwd_f32(const float* flow, const float* mask, const floa
     return USF_EINVAL;
   }
   if (!grad_flow && !grad_mask) return 0;
+  if (!check_align(fn, {{"flow", flow, 16},
+                        {"mask", mask, 16},
+                        {"grad_out", grad_out, 16},
+                        {"grad_flow", grad_flow, 16},
+                        {"grad_mask", grad_mask, 16},
+                        {"scratch", grad_flow ? scratch : nullptr, 16}}))
+    return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn,
                 convex_bwd_launch(flow, mask, grad_out, grad_flow, grad_mask, scratch, B, H, W, factor,
@@ -1257,6 +1402,10 @@ int usf_convex_upsample_pyramid_f32(int nlevel, const float* const* flow, const 
       set_error("%s: level %d: null pointer", fn, l);
       return USF_EINVAL;
     }
+  if (!check_align_each(fn, "flow", (const void* const*)flow, nlevel, 16) ||
+      !check_align_each(fn, "mask", (const void* const*)mask, nlevel, 16) ||
+      !check_align_each(fn, "out", (const void* const*)out, nlevel, 16))
+    return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn, convex_pyr_fwd_launch(nlevel, flow, mask, out, H, W, B, factor, mask_scale, (hipStream_t)stream),
                 (hipStream_t)stream);
@@ -1284,6 +1433,13 @@ int usf_convex_upsample_pyramid_bwd_f32(int nlevel, const float* const* flow, co
     return USF_EINVAL;
   }
   if (!grad_flow && !grad_mask) return 0;
+  if (!check_align_each(fn, "flow", (const void* const*)flow, nlevel, 16) ||
+      !check_align_each(fn, "mask", (const void* const*)mask, nlevel, 16) ||
+      !check_align_each(fn, "grad_out", (const void* const*)grad_out, nlevel, 16) ||
+      !check_align_each(fn, "grad_flow", (const void* const*)grad_flow, nlevel, 16) ||
+      !check_align_each(fn, "grad_mask", (const void* const*)grad_mask, nlevel, 16) ||
+      !check_align(fn, {{"scratch", grad_flow ? scratch : nullptr, 16}}))
+    return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn,
                 convex_pyr_bwd_launch(nlevel, flow, mask, grad_out, grad_flow, grad_mask, scratch, H, W, B, factor,
@@ -1304,6 +1460,7 @@ int usf_area_pyramid_f32(const float* x, float* out1, float* out2, float* out3, 
     set_error("%s: null pointer", fn);
     return USF_EINVAL;
   }
+  if (!check_align(fn, {{"x", x, 16}, {"out1", out1, 16}, {"out2", out2, 16}, {"out3", out3, 16}})) return USF_EINVAL;
   if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
   return finish(fn, area_pyramid_launch(x, out1, out2, out3, (long long)B * C, H, W, (hipStream_t)stream),
                 (hipStream_t)stream);

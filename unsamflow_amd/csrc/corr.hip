@@ -1458,7 +1458,8 @@ template <int D, int PX = 4, int SEGX = 8, int NW = 3, int CC = 4, int NB = 2>
 hipError_t launch_bwd(const float* x1, const float* x2, const float* g, float* gx1, float* gx2,
                       int B, int C, int H, int W, hipStream_t s, BwdEpi ep) {
   if constexpr (Layout<PX, SEGX, D>::X4) {
-    if (W % 4 == 0)
+    // the 16-byte g loads need every sample's slice on a 16-byte boundary too
+    if (W % 4 == 0 && (ep.g_bstride & 3) == 0)
       return launch_bwd_v<D, PX, SEGX, NW, CC, 4, NB>(x1, x2, g, gx1, gx2, B, C, H, W, s, ep);
   }
   return launch_bwd_v<D, PX, SEGX, NW, CC, 1, NB>(x1, x2, g, gx1, gx2, B, C, H, W, s, ep);
@@ -1521,7 +1522,10 @@ __global__ __launch_bounds__(256) void leaky_bwd_gather_kernel(const float* __re
   const float* gb = g + (size_t)b * gbs;
   const float* ab = act + (size_t)b * gbs;
   float* ob = out + (size_t)b * per;
-  if (i + 3 < per && (gbs & 3) == 0) {
+  // 16-byte runs only where every sample's block starts on a 16-byte boundary on
+  // both sides: per % 4 == 0 (the dense output, and the slice's plane offset
+  // inside its parent) and gbs % 4 == 0; i % 4 == 0 and per % 4 == 0 give i + 3 < per
+  if ((per & 3) == 0 && (gbs & 3) == 0) {
     const float4 gv = *reinterpret_cast<const float4*>(gb + i);
     const float4 av = *reinterpret_cast<const float4*>(ab + i);
     *reinterpret_cast<float4*>(ob + i) =

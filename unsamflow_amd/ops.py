@@ -39,6 +39,17 @@ def _require_device_f32(name: str, t: torch.Tensor) -> None:
 def _check_out(name: str, t: torch.Tensor, shape, device) -> None:
     if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or t.device != device or not t.is_contiguous():
         raise ValueError(f"{name} must be a contiguous float32 {tuple(shape)} tensor on {device}")
+    if t.data_ptr() % 16:
+        raise ValueError(f"{name} must be 16-byte aligned (it is written in place; pass a fresh allocation)")
+
+
+def _dense16(t: torch.Tensor) -> torch.Tensor:
+    """``t`` dense and on a 16-byte boundary: what the C ABI asks of every dense
+    tensor parameter (include/unsamflow_hip*.h, "Alignment"). A contiguous tensor
+    at such an address -- every fresh allocation -- is returned as is, no copy; a
+    batch slice of an odd-sized tensor (contiguous, 4-byte aligned) is copied once."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
 def _nchw(name: str, t: torch.Tensor) -> tuple[int, int, int, int]:
@@ -61,7 +72,7 @@ def corr_forward(x1: torch.Tensor, x2: torch.Tensor, max_displacement: int,
         raise ValueError("input1 and input2 are on different devices")
     d = int(max_displacement)
     K = 2 * d + 1
-    x1c, x2c = x1.contiguous(), x2.contiguous()
+    x1c, x2c = _dense16(x1), _dense16(x2)
     if out is None:
         out = torch.empty((B, K * K, H, W), device=x1.device, dtype=torch.float32)
     else:
@@ -112,7 +123,7 @@ def corr_backward(
         raise ValueError(f"grad_output shape {tuple(grad_out.shape)} != {(B, K * K, H, W)}")
     if not (need_x1 or need_x2):
         return None, None
-    x1c, x2c, gc = x1.contiguous(), x2.contiguous(), grad_out.contiguous()
+    x1c, x2c, gc = _dense16(x1), _dense16(x2), _dense16(grad_out)
     g1 = g2 = None
     if need_x1:
         g1 = torch.empty_like(x1c) if gx1_out is None else gx1_out
@@ -157,7 +168,7 @@ def warp_forward(x: torch.Tensor, flow: torch.Tensor, pad: str = "border") -> to
         raise NotImplementedError(f"flow_warp padding mode {pad!r} (supported: border, zeros)")
     if flow.device != x.device:
         raise ValueError("x and flow12 are on different devices")
-    xc = x.contiguous()
+    xc = _dense16(x)
     fv, fbs = _flow_view(flow, B, H, W)
     out = torch.empty_like(xc)
     lib = _lib.load()
@@ -387,9 +398,9 @@ def warp_backward(
         raise ValueError(f"grad_output shape {tuple(grad_out.shape)} != {(B, C, H, W)}")
     if not (need_x or need_flow):
         return None, None
-    xc = x.contiguous()
+    xc = _dense16(x)
     fv, fbs = _flow_view(flow, B, H, W)
-    gc = grad_out.contiguous()
+    gc = _dense16(grad_out)
     gx = torch.empty_like(xc) if need_x else None  # overwritten by the library
     gf = torch.empty((B, 2, H, W), device=x.device, dtype=torch.float32) if need_flow else None
     lib = _lib.load()
@@ -561,13 +572,13 @@ def _loss_images(kind, src, tgt, mask):
         raise NotImplementedError(f"fused census loss needs C = 3 image channels, got {C}")
     if kind.census_rule and (H < 3 or W < 3):
         raise ValueError(f"fused census loss needs H, W >= 3 (an interior pixel), got {(H, W)}")
-    return src.contiguous(), tgt.contiguous(), mask.contiguous(), B, C, H, W
+    return _dense16(src), _dense16(tgt), _dense16(mask), B, C, H, W
 
 
 def _loss_pair_args(kind, flow, im1, im2, mask1, mask2):
     a, b_, m1, B, C, H, W = _loss_images(kind, im1, im2, mask1)
-    m2 = mask2.contiguous()
-    _require_device_f32("mask2", m2)
+    _require_device_f32("mask2", mask2)
+    m2 = _dense16(mask2)
     _require_device_f32("flow", flow)
     if tuple(m2.shape) != (B, 1, H, W):
         raise ValueError(f"mask2 {tuple(m2.shape)} does not match {(B, 1, H, W)}")
@@ -642,7 +653,7 @@ def _loss_pyramid_backward(kind, bases, coef, grad_losses):
     gl = grad_losses.reshape(-1).to(torch.float32).contiguous()
     if gl.numel() != 2 * n or coef.numel() != 2 * kind.nout * n:
         raise ValueError(f"grad_losses / coef sizes {gl.numel()} / {coef.numel()} for {n} scales")
-    bases = [t.contiguous() for t in bases]
+    bases = [_dense16(t) for t in bases]
     coef = coef.contiguous()
     gflows = [torch.empty((B, 4) + tuple(t.shape[2:]), device=dev, dtype=torch.float32) for t in bases]
     ptrs = lambda ts: _host_array(ctypes.c_void_p, [t.data_ptr() for t in ts])  # noqa: E731
@@ -662,7 +673,7 @@ def _loss_backward(kind, basis, coef, grad_loss):
     if K not in (P, 2 * P):
         raise ValueError(f"gradient basis must be [B,{P},H,W] or [B,{2 * P},H,W], got {tuple(basis.shape)}")
     ndir = K // P
-    basis = basis.contiguous()
+    basis = _dense16(basis)
     coef = coef.contiguous()
     gl = grad_loss.reshape(-1).to(torch.float32).contiguous()
     if gl.numel() != ndir or coef.numel() != kind.nout * ndir:
@@ -772,11 +783,11 @@ def ar_transform(img1, img2, flow, mask, theta, noise1=None, noise2=None):
             _require_device_f32(n, t)
             if tuple(t.shape) != (B, 3, H, W):
                 raise ValueError(f"{n} {tuple(t.shape)} does not match {(B, 3, H, W)}")
-            t = t.contiguous()
+            t = _dense16(t)
         noise.append(t)
     if any(t.device != dev for t in (img2, flow, mask, theta) + tuple(t for t in noise if t is not None)):
         raise ValueError("the spatial transform's tensors are on different devices")
-    a, b_, m, th = img1.contiguous(), img2.contiguous(), mask.contiguous(), theta.contiguous()
+    a, b_, m, th = _dense16(img1), _dense16(img2), _dense16(mask), theta.contiguous()
     fv, fbs = _flow_view(flow, B, H, W)
     outs = (torch.empty_like(a), torch.empty_like(b_), torch.empty((B, 2, H, W), device=dev, dtype=torch.float32),
             torch.empty_like(m))
@@ -912,7 +923,7 @@ def fakeobj_paste_crop(img1, img2, flow, noc, cache_mask, cache_img, cache_motio
         raise ValueError(f"crop {(ch, cw)} at {(y0, x0)} lies outside the image {(H, W)}")
     if any(t.device != dev for t in (img2, flow, noc, cache_mask, cache_img)):
         raise ValueError("the object insertion's tensors are on different devices")
-    a, b_, nc = img1.contiguous(), img2.contiguous(), noc.contiguous()
+    a, b_, nc = _dense16(img1), _dense16(img2), _dense16(noc)
     fv, fbs = _flow_view(flow, B, H, W)
     outs = (torch.empty((B, 6, ch, cw), device=dev, dtype=torch.float32),
             torch.empty((B, 2, ch, cw), device=dev, dtype=torch.float32),
@@ -949,7 +960,7 @@ def fakeobj_push(obj_mask, img, flow, slots, cache_mask, cache_img, cache_motion
     _fakeobj_table("slots", slots, (B,), torch.int32, dev)
     if any(t.device != dev for t in (obj_mask, flow, cache_mask, cache_img)):
         raise ValueError("the object cache's tensors are on different devices")
-    m, im = obj_mask.contiguous(), img.contiguous()
+    m, im = _dense16(obj_mask), _dense16(img)
     fv, fbs = _flow_view(flow, B, H, W)
     lib = _lib.load()
     partials = torch.empty(lib.usf_fakeobj_push_partials(B, H, W), device=dev, dtype=torch.float32)
@@ -974,7 +985,7 @@ def _segpool_args(proj, seg, num_segments):
     K = int(num_segments)
     if not 1 <= K <= _lib.SEGPOOL_MAX_K:
         raise ValueError(f"num_segments={K} outside [1, {_lib.SEGPOOL_MAX_K}] (USF_SEGPOOL_MAX_K)")
-    return proj.contiguous(), seg.contiguous(), B, C, H, W, K
+    return _dense16(proj), _dense16(seg), B, C, H, W, K
 
 
 def segpool_forward(proj, seg, num_segments: int):
@@ -1010,7 +1021,7 @@ def segpool_backward(proj, seg, state, grad_spread, num_segments: int):
     if (state.dtype != torch.int32 or state.device != dev or not state.is_contiguous()
             or state.numel() != lib.usf_segpool_state_words(B, C, K)):
         raise ValueError("state is not the forward's table buffer for this shape")
-    g = grad_spread.contiguous()
+    g = _dense16(grad_spread)
     gproj = torch.empty_like(p)
     _args = (p.data_ptr(), s.data_ptr(), state.data_ptr(), g.data_ptr(), gproj.data_ptr(), B, C, H, W, K,
              _lib.stream_handle(dev),)
@@ -1026,7 +1037,7 @@ def _hg_args(flow, seg):
     _require_device_f32("full_seg", seg)
     if tuple(seg.shape) != (B, 1, H, W) or seg.device != fv.device:
         raise ValueError(f"full_seg must be [B,1,h,w] = {(B, 1, H, W)} on {fv.device}, got {tuple(seg.shape)}")
-    return fv, fbs, seg.contiguous(), B, H, W
+    return fv, fbs, _dense16(seg), B, H, W
 
 
 def _hg_records(records, B, dev):
@@ -1048,7 +1059,7 @@ def hg_fit(flow, seg, occ, num_segments: int, thr: float, n_hyp: int = _lib.HG_D
     _require_device_f32("occ_mask", occ)
     if tuple(occ.shape) != (B, 1, H, W) or occ.device != dev:
         raise ValueError(f"occ_mask must be [B,1,h,w] = {(B, 1, H, W)} on {dev}, got {tuple(occ.shape)}")
-    o = occ.contiguous()
+    o = _dense16(occ)
     K, n_hyp = int(num_segments), int(n_hyp)
     if not 1 <= K <= _lib.HG_MAX_K:
         raise ValueError(f"num_segments={K} outside [1, {_lib.HG_MAX_K}] (USF_HG_MAX_K)")
@@ -1155,7 +1166,9 @@ def corr_forward_ex(x1: torch.Tensor, x2: torch.Tensor, max_displacement: int, o
     d = int(max_displacement)
     K = 2 * d + 1
     obs = _plane_slice_stride("output", out, (B, K * K, H, W))
-    x1c, x2c = x1.contiguous(), x2.contiguous()
+    if out.data_ptr() % (16 if H * W % 4 == 0 else 4):
+        raise ValueError("output must be a channel slice of a 16-byte aligned NCHW buffer")
+    x1c, x2c = _dense16(x1), _dense16(x2)
     lib = _lib.load()
     act = 0 if leaky_slope is None else 1
     if act_mask is not None:
@@ -1209,7 +1222,7 @@ def corr_backward_ex(x1: torch.Tensor, x2: torch.Tensor, grad_out: torch.Tensor,
             scratch = torch.empty(n, device=x1.device, dtype=torch.float32)
     if not (need_x1 or need_x2):
         return None, None
-    x1c, x2c = x1.contiguous(), x2.contiguous()
+    x1c, x2c = _dense16(x1), _dense16(x2)
     g1 = torch.empty_like(x1c) if need_x1 else None
     g2 = torch.empty_like(x2c) if need_x2 else None
     # with the LeakyReLU derivative the site also reads the activated output
@@ -1237,7 +1250,7 @@ def flow_upsample(flow: torch.Tensor, factor: int) -> torch.Tensor:
     _require_device_f32("flow", flow)
     B, C, H, W = _nchw("flow", flow)
     k = int(factor)
-    fc = flow.contiguous()
+    fc = _dense16(flow)
     out = torch.empty((B, C, H * k, W * k), device=flow.device, dtype=torch.float32)
     lib = _lib.load()
     _args = (fc.data_ptr(), out.data_ptr(), B, C, H, W, k, _lib.stream_handle(flow.device),)
@@ -1260,7 +1273,7 @@ def warp_forward_up(x: torch.Tensor, coarse_flow: torch.Tensor, pad: str = "bord
         raise NotImplementedError(f"flow_warp padding mode {pad!r} (supported: border, zeros)")
     if tuple(coarse_flow.shape) != (B, 2, H // 2, W // 2) or H % 2 or W % 2:
         raise ValueError(f"coarse flow shape {tuple(coarse_flow.shape)} is not [B,2,H/2,W/2] of x {(B, C, H, W)}")
-    xc, fc = x.contiguous(), coarse_flow.contiguous()
+    xc, fc = _dense16(x), _dense16(coarse_flow)
     up = torch.empty((B, 2, H, W), device=x.device, dtype=torch.float32)
     out = torch.empty_like(xc)
     lib = _lib.load()
@@ -1282,14 +1295,14 @@ def flow_upsample_backward(grad_out: torch.Tensor, factor: int, grad_out2: torch
     if Ho % k or Wo % k:
         raise ValueError(f"grad_out spatial size {(Ho, Wo)} is not a multiple of {k}")
     H, W = Ho // k, Wo // k
-    gc = grad_out.contiguous()
+    gc = _dense16(grad_out)
     gx = torch.empty((B, C, H, W), device=grad_out.device, dtype=torch.float32)
     lib = _lib.load()
     if grad_out2 is not None:
         _require_device_f32("grad_out2", grad_out2)
         if grad_out2.shape != grad_out.shape:
             raise ValueError(f"grad_out2 shape {tuple(grad_out2.shape)} != {tuple(grad_out.shape)}")
-        g2 = grad_out2.contiguous()
+        g2 = _dense16(grad_out2)
         _args = (gc.data_ptr(), g2.data_ptr(), gx.data_ptr(), B, C, H, W, k, _lib.stream_handle(grad_out.device),)
         with torch.cuda.device(grad_out.device), _kt.timed("upsample_bwd", (B, C, H, W, k), grad_out.device,
                                                              4 * B * C * H * W * (1 + 2 * k * k)):
@@ -1315,7 +1328,7 @@ def convex_upsample(flow: torch.Tensor, mask: torch.Tensor, factor: int = 4,
     if C != 2 or tuple(mask.shape) != (B, 9 * f * f, H, W):
         raise ValueError(f"convex_upsample: flow {tuple(flow.shape)} / mask {tuple(mask.shape)} (want [B,2,H,W] / "
                          f"[B,{9 * f * f},H,W])")
-    fc, mc = flow.contiguous(), mask.contiguous()
+    fc, mc = _dense16(flow), _dense16(mask)
     out = torch.empty((B, 2, f * H, f * W), device=flow.device, dtype=torch.float32)
     lib = _lib.load()
     nbytes = 4 * B * H * W * (2 + 11 * f * f)
@@ -1337,7 +1350,7 @@ def convex_upsample_backward(flow: torch.Tensor, mask: torch.Tensor, grad_out: t
         raise ValueError(f"convex_upsample_backward: grad_out {tuple(grad_out.shape)}")
     if not (need_flow or need_mask):
         return None, None
-    fc, mc, gc = flow.contiguous(), mask.contiguous(), grad_out.contiguous()
+    fc, mc, gc = _dense16(flow), _dense16(mask), _dense16(grad_out)
     gf = torch.empty((B, 2, H, W), device=flow.device, dtype=torch.float32) if need_flow else None
     gm = torch.empty_like(mc) if need_mask else None
     lib = _lib.load()
@@ -1369,8 +1382,8 @@ def convex_upsample_pyramid(flows, masks, factor: int = 4, mask_scale: float = 0
     import ctypes
 
     n = len(flows)
-    fl = [f.contiguous() for f in flows]
-    mk = [m.contiguous() for m in masks]
+    fl = [_dense16(f) for f in flows]
+    mk = [_dense16(m) for m in masks]
     for f, m in zip(fl, mk):
         _require_device_f32("flow", f)
         _require_device_f32("mask", m)
@@ -1395,9 +1408,9 @@ def convex_upsample_pyramid_backward(flows, masks, grad_outs, factor: int = 4, m
     import ctypes
 
     n = len(flows)
-    fl = [f.contiguous() for f in flows]
-    mk = [m.contiguous() for m in masks]
-    go = [g.contiguous() for g in grad_outs]
+    fl = [_dense16(f) for f in flows]
+    mk = [_dense16(m) for m in masks]
+    go = [_dense16(g) for g in grad_outs]
     B, f_ = fl[0].shape[0], int(factor)
     if not (need_flow or need_mask):
         return None, None
@@ -1429,7 +1442,7 @@ def area_pyramid(x: torch.Tensor):
     B, C, H, W = _nchw("x", x)
     if H % 8 or W % 8:
         raise ValueError(f"area_pyramid needs H, W multiples of 8, got {H}x{W}")
-    xc = x.contiguous()
+    xc = _dense16(x)
     outs = [torch.empty((B, C, H >> s, W >> s), device=x.device, dtype=torch.float32) for s in (1, 2, 3)]
     lib = _lib.load()
     nbytes = 4 * B * C * H * W * (1 + 1 / 4 + 1 / 16 + 1 / 64)
@@ -1447,6 +1460,8 @@ def _conv_epi_args(y, bias, slope):
     B, C, H, W = _nchw("y", y)
     if not y.is_contiguous():
         raise ValueError(f"y must be dense NCHW (strides {y.stride()})")
+    if y.data_ptr() % 16:
+        raise ValueError("y must be 16-byte aligned (it is updated in place)")
     if tuple(bias.shape) != (C,) or bias.device != y.device:
         raise ValueError(f"bias must be [{C}] on {y.device}, got {tuple(bias.shape)} on {bias.device}")
     slope = float(slope)
@@ -1497,6 +1512,7 @@ def conv_epilogue_backward(grad_out: torch.Tensor, y: torch.Tensor | None, slope
         _require_device_f32("y", y)
         if tuple(y.shape) != (B, C, H, W) or y.device != dev or not y.is_contiguous():
             raise ValueError(f"y must be a dense {(B, C, H, W)} tensor on {dev}")
+        y = _dense16(y)
     elif y is not None:
         raise ValueError("y must be None without an activation (slope == 1)")
     if not act and not need_bias:
