@@ -284,6 +284,25 @@ FAKEOBJ_SYMBOLS = {
     ),
 }
 
+# validation on the device (include/unsamflow_hip_eval.h), versioned the same way
+EVAL_API_VERSION = 1
+EVAL_NACC = 12
+EVAL_NMETRIC = 7
+DEVERR_EVAL_BAD_SIZE = 32
+EVAL_SYMBOLS = {
+    "usf_eval_api_version": ([], ctypes.c_int),
+    "usf_flow_resize_f32": (
+        [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, _c_float_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+    "usf_flow_eval_partials": ([ctypes.c_int] * 3, ctypes.c_int),
+    "usf_flow_eval_f32": (
+        [_c_float_p, ctypes.c_longlong, _c_float_p, ctypes.c_int, _c_float_p, ctypes.c_void_p] + [_c_float_p] * 3
+        + [ctypes.c_int] * 5 + [ctypes.c_void_p],
+        ctypes.c_int,
+    ),
+}
+
 _lock = threading.Lock()
 _lib = None
 _load_error: str | None = None
@@ -309,7 +328,8 @@ def load() -> ctypes.CDLL:
             raise RuntimeError(_load_error)
         lib = ctypes.CDLL(str(_LIB_PATH), mode=ctypes.RTLD_LOCAL)
         for name, (argtypes, restype) in {**_SIGNATURES, **CENSUS_SYMBOLS, **AR_SYMBOLS, **SEGPOOL_SYMBOLS,
-                                          **HG_SYMBOLS, **CONVEPI_SYMBOLS, **FAKEOBJ_SYMBOLS}.items():
+                                          **HG_SYMBOLS, **CONVEPI_SYMBOLS, **FAKEOBJ_SYMBOLS,
+                                          **EVAL_SYMBOLS}.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = restype
@@ -334,6 +354,9 @@ def load() -> ctypes.CDLL:
         v = lib.usf_fakeobj_api_version()
         if v != FAKEOBJ_API_VERSION:
             raise RuntimeError(f"libunsamflow_hip.so fake-object API version {v} != expected {FAKEOBJ_API_VERSION}")
+        v = lib.usf_eval_api_version()
+        if v != EVAL_API_VERSION:
+            raise RuntimeError(f"libunsamflow_hip.so evaluation API version {v} != expected {EVAL_API_VERSION}")
         _lib = lib
         return lib
 

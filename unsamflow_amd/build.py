@@ -24,10 +24,10 @@ INCLUDE_DIR = PKG_DIR.parent / "include"
 ARCH = os.environ.get("USF_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-SOURCES = ["corr.hip", "warp.hip", "occ.hip", "photo.hip", "census.hip", "ar.hip", "fakeobj.hip", "segpool.hip", "hg.hip", "upsample.hip", "convex.hip", "convepi.hip", "stream.hip", "capi.cpp"]
-HEADERS = ["usf_common.h", "warp_tap.h", "interp_tap.h", "strip.h", "wave.h", "scatter_rows.h", "seg_key.h"]
+SOURCES = ["corr.hip", "warp.hip", "occ.hip", "photo.hip", "census.hip", "ar.hip", "fakeobj.hip", "eval.hip", "segpool.hip", "hg.hip", "upsample.hip", "convex.hip", "convepi.hip", "stream.hip", "capi.cpp"]
+HEADERS = ["usf_common.h", "warp_tap.h", "interp_tap.h", "strip.h", "wave.h", "scatter_rows.h", "seg_key.h", "resize_tap.h"]
 PUBLIC_HEADERS = ["unsamflow_hip.h", "unsamflow_hip_census.h", "unsamflow_hip_ar.h", "unsamflow_hip_segpool.h",
-                  "unsamflow_hip_hg.h", "unsamflow_hip_convepi.h", "unsamflow_hip_fakeobj.h"]  # the C ABI (include/)
+                  "unsamflow_hip_hg.h", "unsamflow_hip_convepi.h", "unsamflow_hip_fakeobj.h", "unsamflow_hip_eval.h"]  # the C ABI (include/)
 
 # -fno-slp-vectorize: the SLP vectorizer packs the kernels' independent FMAs into
 # v_pk_fma_f32 / v_pk_add_f32, whose operands must sit in aligned register pairs:

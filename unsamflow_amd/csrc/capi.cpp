@@ -14,6 +14,7 @@
 #include "../../include/unsamflow_hip_ar.h"
 #include "../../include/unsamflow_hip_census.h"
 #include "../../include/unsamflow_hip_convepi.h"
+#include "../../include/unsamflow_hip_eval.h"
 #include "../../include/unsamflow_hip_fakeobj.h"
 #include "../../include/unsamflow_hip_hg.h"
 #include "../../include/unsamflow_hip_segpool.h"
@@ -117,11 +118,12 @@ static int finish(const char* fn, hipError_t e, hipStream_t s) {
   if (e == hipSuccess && sync_check_on(s)) {
     e = hipStreamSynchronize(s);
     if (e != hipSuccess) fprintf(stderr, "[usf] %s: fault after launch: %s\n", fn, hipGetErrorString(e));
-    // a bad segment id or cache slot is the caller's data, not a failed launch: left for usf_device_errors
-    const int flags =
-        e == hipSuccess
-            ? device_errors(s, true, ~(USF_DEVERR_SEGPOOL_BAD_ID | USF_DEVERR_HG_BAD_ID | USF_DEVERR_FAKEOBJ_BAD_SLOT))
-            : 0;
+    // a bad segment id, cache slot or sample size is the caller's data, not a failed launch: left for
+    // usf_device_errors
+    const int flags = e == hipSuccess ? device_errors(s, true,
+                                                      ~(USF_DEVERR_SEGPOOL_BAD_ID | USF_DEVERR_HG_BAD_ID |
+                                                        USF_DEVERR_FAKEOBJ_BAD_SLOT | USF_DEVERR_EVAL_BAD_SIZE))
+                                      : 0;
     if (flags > 0) {
       fprintf(stderr, "[usf] %s: device error flags 0x%x\n", fn, flags);
       set_error("%s: device error flags 0x%x", fn, flags);
@@ -1046,6 +1048,83 @@ int usf_fakeobj_push_f32(const float* obj_mask, const float* img, const float* f
   return finish(fn,
                 fakeobj_push_launch(obj_mask, img, flow, flow_bstride, slot, cache_mask, cache_img, cache_motion,
                                     partials, B, H, W, cache_size, (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+// --------------------------------------------------- unsamflow_hip_eval.h --
+int usf_eval_api_version(void) { return USF_EVAL_API_VERSION; }
+
+// shapes and the prediction's stride of both evaluation entries
+static bool check_eval(const char* fn, int B, int h, int w, int Hmax, int Wmax, long long pbs) {
+  if (B < 1 || B > 65535) {
+    set_error("%s: B=%d outside [1, 65535]", fn, B);
+    return false;
+  }
+  if (h < 2 || w < 2 || Hmax < 2 || Wmax < 2) {
+    set_error("%s: h=%d w=%d Hmax=%d Wmax=%d (the align_corners resize needs every size >= 2)", fn, h, w, Hmax, Wmax);
+    return false;
+  }
+  if (!check_dims(fn, B, 2, h, w) || !check_dims(fn, B, 5, Hmax, Wmax)) return false;
+  if (pbs < 2LL * h * w && B > 1) {
+    set_error("%s: prediction batch stride %lld < 2*h*w", fn, pbs);
+    return false;
+  }
+  return true;
+}
+
+int usf_flow_resize_f32(const float* pred, long long pred_bstride, const int* sizes, float* out, int B, int h, int w,
+                        int Hmax, int Wmax, void* stream) {
+  clear_error();
+  const char* fn = "usf_flow_resize_f32";
+  if (!check_eval(fn, B, h, w, Hmax, Wmax, pred_bstride)) return USF_EINVAL;
+  if (!pred) {
+    set_error("%s: null input pointer", fn);
+    return USF_EINVAL;
+  }
+  if (!out) {
+    set_error("%s: null output pointer", fn);
+    return USF_EINVAL;
+  }
+  if (!check_align(fn, {{"pred", pred, 4}, {"sizes", sizes, 4}, {"out", out, 16}})) return USF_EINVAL;
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn, flow_resize_launch(pred, pred_bstride, sizes, out, B, h, w, Hmax, Wmax, (hipStream_t)stream),
+                (hipStream_t)stream);
+}
+
+int usf_flow_eval_partials(int B, int Hmax, int Wmax) {
+  return (B > 0 && Hmax > 0 && Wmax > 0) ? flow_eval_partials(B, Hmax, Wmax) : 0;
+}
+
+int usf_flow_eval_f32(const float* pred, long long pred_bstride, const float* gt, int Cg, const float* move,
+                      const int* sizes, float* partials, float* sums, float* metrics, int B, int h, int w, int Hmax,
+                      int Wmax, void* stream) {
+  clear_error();
+  const char* fn = "usf_flow_eval_f32";
+  if (!check_eval(fn, B, h, w, Hmax, Wmax, pred_bstride)) return USF_EINVAL;
+  if (Cg != 2 && Cg != 4) {
+    set_error("%s: Cg=%d ground-truth channels (2: u, v; 4: u, v, valid, noc)", fn, Cg);
+    return USF_EINVAL;
+  }
+  if (!pred || !gt) {
+    set_error("%s: null input pointer", fn);
+    return USF_EINVAL;
+  }
+  if (!partials || !sums || !metrics) {
+    set_error("%s: null output pointer", fn);
+    return USF_EINVAL;
+  }
+  if (!check_align(fn, {{"pred", pred, 4},
+                        {"gt", gt, 16},
+                        {"move", move, 16},
+                        {"sizes", sizes, 4},
+                        {"partials", partials, 16},
+                        {"sums", sums, 16},
+                        {"metrics", metrics, 16}}))
+    return USF_EINVAL;
+  if (const int pe = pre_check(fn, (hipStream_t)stream)) return pe;
+  return finish(fn,
+                flow_eval_launch(pred, pred_bstride, gt, Cg, move, sizes, partials, sums, metrics, B, h, w, Hmax, Wmax,
+                                 (hipStream_t)stream),
                 (hipStream_t)stream);
 }
 

@@ -226,6 +226,15 @@ hipError_t fakeobj_push_launch(const float* mask, const float* img, const float*
                                float* cmask, float* cimg, float* cmotion, float* partials, int B, int H, int W,
                                int cache_size, hipStream_t s);
 
+// eval.hip: validation (per-sample flow resize; the fused EPE / Fl sums and their finalisation)
+int eval_device_errors(bool clear);  // this code object's flags (device_errors() adds them)
+hipError_t flow_resize_launch(const float* pred, long long pbs, const int* sizes, float* out, int B, int h, int w,
+                              int Hmax, int Wmax, hipStream_t s);
+int flow_eval_partials(int B, int Hmax, int Wmax);
+hipError_t flow_eval_launch(const float* pred, long long pbs, const float* gt, int Cg, const float* move,
+                            const int* sizes, float* partials, float* sums, float* metrics, int B, int h, int w,
+                            int Hmax, int Wmax, hipStream_t s);
+
 // convepi.hip: the conv epilogues (bias + LeakyReLU in place; their backward with the bias gradient)
 long long convepi_bwd_workspace(int B, int C, int H, int W);  // floats; -1: shape not taken
 hipError_t convepi_fwd_launch(float* y, const float* bias, int B, int C, int H, int W, float slope, hipStream_t s);

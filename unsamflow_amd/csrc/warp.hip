@@ -28,6 +28,7 @@
 #include "interp_tap.h"
 #include "scatter_rows.h"
 #include "usf_common.h"
+#include "../../include/unsamflow_hip_eval.h"
 #include "../../include/unsamflow_hip_fakeobj.h"
 #include "../../include/unsamflow_hip_hg.h"
 #include "../../include/unsamflow_hip_segpool.h"
@@ -1313,11 +1314,12 @@ int device_errors(hipStream_t s, bool clear, int mask) {
   if (hipStreamSynchronize(s) != hipSuccess) return -1;
   const int v = read_clear_flags(HIP_SYMBOL(g_dev_errors), clear, mask);
   if (v < 0) return -1;
-  // segpool.hip, hg.hip and fakeobj.hip keep their own flag words (one code object per source file)
+  // segpool.hip, hg.hip, fakeobj.hip and eval.hip keep their own flag words (one code object per source file)
   const int sp = (mask & USF_DEVERR_SEGPOOL_BAD_ID) ? segpool_device_errors(clear) : 0;
   const int hg = (mask & USF_DEVERR_HG_BAD_ID) ? hg_device_errors(clear) : 0;
   const int fo = (mask & USF_DEVERR_FAKEOBJ_BAD_SLOT) ? fakeobj_device_errors(clear) : 0;
-  return (sp < 0 || hg < 0 || fo < 0) ? -1 : (v | sp | hg | fo);
+  const int ev = (mask & USF_DEVERR_EVAL_BAD_SIZE) ? eval_device_errors(clear) : 0;
+  return (sp < 0 || hg < 0 || fo < 0 || ev < 0) ? -1 : (v | sp | hg | fo | ev);
 }
 
 hipError_t warp_fwd_launch(const float* x, const float* flow, long long fbs, float* out, int B,

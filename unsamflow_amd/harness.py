@@ -371,3 +371,78 @@ class GraphedTrainStep:
         self.step.scheduler.step()
         return self.loss
 
+
+
+def synthetic_flow_gt(B: int, sizes, device, seed: int = 42):
+    """Ragged validation ground truth as KITTI's loader yields it, padded into
+    one batch: ``sizes`` a list of B (H_b, W_b) -> (gt [B,4,Hmax,Wmax] float32
+    planar (u, v, valid, noc), zero outside each sample's window, Wmax rounded up
+    to a multiple of 4 as evaluate.pad_ground_truth does; size table [B,2]
+    int32), both on ``device``. u, v ~ 8 N(0,1) px; about 60 % of the
+    pixels are valid (KITTI's ground truth is sparse) and 75 % of those are
+    non-occluded."""
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    if len(sizes) != B:
+        raise ValueError(f"{len(sizes)} sizes for a batch of {B}")
+    Hmax, Wmax = max(h for h, _ in sizes), (max(w for _, w in sizes) + 3) // 4 * 4
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    gt = torch.zeros(B, 4, Hmax, Wmax)
+    for b, (h, w) in enumerate(sizes):
+        gt[b, :2, :h, :w] = torch.randn(2, h, w, generator=g) * 8.0
+        valid = (torch.rand(h, w, generator=g) < 0.6).float()
+        gt[b, 2, :h, :w] = valid
+        gt[b, 3, :h, :w] = valid * (torch.rand(h, w, generator=g) < 0.75).float()
+    return gt.to(device), torch.tensor(sizes, dtype=torch.int32).to(device)
+
+
+class Validator:
+    """The reference's ``_validate_with_gt`` (trainer/kitti_trainer_ar.py:360-402,
+    trainer/sintel_trainer_ar.py:343-378) without its per-batch device-to-host
+    copy and numpy loop: every batch runs ``model(img1, img2, with_bk=False)``
+    under ``torch.no_grad()`` in ``eval()`` mode and feeds ``flows_12[0]`` to
+    :class:`unsamflow_amd.evaluate.FlowMetrics`; the model's mode is restored
+    afterwards. ``step_or_model``: a :class:`TrainStep` (its unwrapped module is
+    used: no DDP traffic in validation) or a module.
+
+    ``metrics="kitti"``: ``gt`` is [B,4,Hmax,Wmax] (u, v, valid, noc) with an
+    optional size table, five numbers (seven with a move mask, "kitti_move").
+    ``metrics="sintel"``: ``gt`` is the flow [B,2,H,W] and ``occ`` the occlusion
+    mask [B,1,H,W]; valid = 1 and noc = 1 - occ as sintel_trainer_ar.py:367-369
+    builds them, and the first three numbers are reported."""
+
+    def __init__(self, step_or_model, metrics: str = "kitti", fused=None):
+        from .evaluate import FlowMetrics
+
+        if metrics not in ("kitti", "kitti_move", "sintel"):
+            raise ValueError(f"metrics must be 'kitti', 'kitti_move' or 'sintel', got {metrics!r}")
+        self.model = getattr(step_or_model, "module", step_or_model)
+        self.kind = metrics
+        self.metrics = FlowMetrics(metrics, fused=fused)
+
+    def reset(self) -> None:
+        self.metrics.reset()
+
+    def update(self, img1, img2, gt, sizes=None, move=None, occ=None, full_seg1=None, full_seg2=None):
+        """One validation batch; returns the prediction ``flows_12[0]``. Nothing
+        here reads the device from the host."""
+        model = self.model
+        was_training = model.training
+        model.eval()
+        try:
+            with torch.no_grad():
+                pred = model(img1, img2, full_seg1, full_seg2, with_bk=False)["flows_12"][0]
+                if self.kind == "sintel":
+                    if occ is None:
+                        raise ValueError("Validator(metrics='sintel') needs the occlusion mask `occ`")
+                    gt = torch.cat([gt[:, :2], torch.ones_like(occ), 1 - occ], dim=1)
+                self.metrics.update(pred, gt, sizes, move)
+        finally:
+            model.train(was_training)
+        return pred
+
+    def all_reduce(self, group=None) -> None:
+        self.metrics.all_reduce(group)
+
+    def compute(self) -> dict:
+        """{name: mean over the validated samples} (the single sync)."""
+        return self.metrics.compute()

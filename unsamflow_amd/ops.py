@@ -974,6 +974,80 @@ def fakeobj_push(obj_mask, img, flow, slots, cache_mask, cache_img, cache_motion
     _lib.check(rc, "usf_fakeobj_push_f32")
 
 
+def _eval_args(pred, sizes, Hmax, Wmax):
+    """Checks shared by the two evaluation entries -> (prediction view, its batch
+    stride, B, h, w, size table or None)."""
+    _require_device_f32("pred", pred)
+    B, C, h, w = _nchw("pred", pred)
+    if C != 2 or h < 2 or w < 2 or Hmax < 2 or Wmax < 2:
+        raise ValueError(f"pred must be [B,2,h,w] with h, w >= 2 and the target at least 2x2, got {tuple(pred.shape)} "
+                         f"-> {(Hmax, Wmax)}")
+    if sizes is not None:
+        _fakeobj_table("sizes", sizes, (B, 2), torch.int32, pred.device)
+    pv, pbs = _flow_view(pred, B, h, w)
+    return pv, pbs, B, h, w, sizes
+
+
+def flow_resize(pred, sizes, Hmax: int, Wmax: int, out=None):
+    """resize_flow (utils/flow_utils.py:62-71) to a size of its own per sample
+    (usf_flow_resize_f32). pred [B,2,h,w] (a channel slice is used in place);
+    sizes [B,2] int32 (H_b, W_b) on the device, or None: every sample is
+    (Hmax, Wmax). -> out [B,2,Hmax,Wmax]: sample b's window [0,H_b) x [0,W_b) is
+    written, the rest keeps what ``out`` held (zeros when allocated here)."""
+    Hmax, Wmax = int(Hmax), int(Wmax)
+    pv, pbs, B, h, w, sizes = _eval_args(pred, sizes, Hmax, Wmax)
+    dev = pred.device
+    if out is None:
+        alloc = torch.empty if sizes is None else torch.zeros
+        out = alloc((B, 2, Hmax, Wmax), device=dev, dtype=torch.float32)
+    else:
+        _check_out("out", out, (B, 2, Hmax, Wmax), dev)
+    lib = _lib.load()
+    _args = (pv.data_ptr(), pbs, _ptr(sizes), out.data_ptr(), B, h, w, Hmax, Wmax, _lib.stream_handle(dev),)
+    # algorithmic bytes: the prediction read once, the output written once
+    with torch.cuda.device(dev), _kt.timed("flow_resize", (B, h, w, Hmax, Wmax), dev,
+                                           4 * B * 2 * (h * w + Hmax * Wmax)):
+        rc = lib.usf_flow_resize_f32(*_args)
+    _lib.check(rc, "usf_flow_resize_f32")
+    return out
+
+
+def flow_eval(pred, gt, sizes=None, move=None):
+    """The error sums and metrics of evaluate_flow (flow_utils.py:117-201) for a
+    batch of ragged ground truths (usf_flow_eval_f32; deterministic). pred
+    [B,2,h,w] (a channel slice is used in place); gt [B,Cg,Hmax,Wmax] planar,
+    Cg = 2 or 4 (u, v, valid, noc); sizes [B,2] int32 on the device or None;
+    move [B,1,Hmax,Wmax] or None -> (metrics [B,7], sums [B,12])."""
+    _require_device_f32("gt", gt)
+    Bg, Cg, Hmax, Wmax = _nchw("gt", gt)
+    pv, pbs, B, h, w, sizes = _eval_args(pred, sizes, Hmax, Wmax)
+    dev = pred.device
+    if Bg != B or Cg not in (2, 4) or gt.device != dev:
+        raise ValueError(f"gt must be [{B},2 or 4,H,W] on {dev}, got {tuple(gt.shape)} on {gt.device}")
+    g = _dense16(gt)
+    m = None
+    if move is not None:
+        _require_device_f32("move", move)
+        if tuple(move.shape) != (B, 1, Hmax, Wmax) or move.device != dev:
+            raise ValueError(f"move {tuple(move.shape)} does not match {(B, 1, Hmax, Wmax)} on {dev}")
+        m = _dense16(move)
+    lib = _lib.load()
+    # scratch of one row per workgroup: no initialisation needed, one per shape and device
+    with torch.cuda.device(dev):
+        partials = persistent_workspace(dev, "flow_eval", (B, Hmax, Wmax),
+                                        4 * lib.usf_flow_eval_partials(B, Hmax, Wmax))
+    metrics = torch.empty((B, _lib.EVAL_NMETRIC), device=dev, dtype=torch.float32)
+    sums = torch.empty((B, _lib.EVAL_NACC), device=dev, dtype=torch.float32)
+    _args = (pv.data_ptr(), pbs, g.data_ptr(), Cg, _ptr(m), _ptr(sizes), partials.data_ptr(), sums.data_ptr(),
+             metrics.data_ptr(), B, h, w, Hmax, Wmax, _lib.stream_handle(dev),)
+    # algorithmic bytes: every ground-truth plane and the move mask read once, the prediction once
+    nbytes = 4 * B * ((Cg + (m is not None)) * Hmax * Wmax + 2 * h * w)
+    with torch.cuda.device(dev), _kt.timed("flow_eval", (B, Cg, h, w, Hmax, Wmax, m is not None), dev, nbytes):
+        rc = lib.usf_flow_eval_f32(*_args)
+    _lib.check(rc, "usf_flow_eval_f32")
+    return metrics, sums
+
+
 def _segpool_args(proj, seg, num_segments):
     _require_device_f32("proj", proj)
     _require_device_f32("seg", seg)
